@@ -80,7 +80,9 @@ typedef struct vg_vit vg_vit;
  *          blocks' ln_1 / ln_2 are folded into the GEMMs around them (gamma-scaled fp16 weights built once per handle at the
  *          first encode, which therefore allocates and synchronises and must not run inside a stream capture);
  *          VG_VIT_LN_FOLD=0 at create time keeps separate LayerNorm kernels.
- * Constraints: width % 128 == 0, width <= 1024, heads * 64 == width, tokens <= 224. */
+ * Constraints: width % 128 == 0, width <= 1024, heads * 64 == width, tokens T = (resolution / patch)^2 + 1 <= 1024 for dtype 1
+ * (T <= 224: k_attention_f16; above: k_attention_f16_long) and T <= 282 for dtype 0 (k_attention_f32's LDS bound).  Any patch size:
+ * the patch-embedding K = 3 * patch^2 is padded to a multiple of 64 (ViT-L/14: 588 -> 640) in conv1.weight and the im2col rows. */
 int vg_vit_create(vg_vit** out, int width, int layers, int heads, int patch, int resolution, int out_dim, int dtype);
 void vg_vit_destroy(vg_vit* v);
 /* one tensor by its reference state_dict name without the 'visual.' prefix (model.py:206-221,171-183);
@@ -92,7 +94,7 @@ int vg_vit_set_input_norm(vg_vit* v, const float* h_mean3, const float* h_std3);
 /* bytes of device workspace for n_crops; the caller zero-fills it once. */
 int64_t vg_vit_workspace_bytes(const vg_vit* v, int n_crops);
 /* d_crops: [n,3,res,res] CHW, input_kind 0 = float32, 1 = float16 (what vg_render_crops out_kind 1/2
- * writes); input_kind 2 = f16 patch rows [n*(res/patch)^2, 3*patch^2] (vg_render_crops out_kind 4, fp16 mode only;
+ * writes); input_kind 2 = f16 patch rows [n*(res/patch)^2, 3*patch^2] (vg_render_crops out_kind 4, fp16 mode and 3*patch^2 % 64 == 0 only;
  * row count must be padded by the caller to a multiple of 256 rows of readable memory); input_kind 3 = f16 single-channel patch rows
  * [n*(res/patch)^2, patch^2] holding level / 256 (vg_render_crops out_kind 5, fp16 mode, patch^2 % 128 == 0): the patch embedding
  * (model.py:223-226 after clip.py:79-86's Normalize) runs as a K = patch^2 GEMM on W1[n,p] = 256/255 sum_c conv1[n,c,p] / std_c with
@@ -106,7 +108,8 @@ int vg_vit_encode(vg_vit* v, const void* d_crops, int input_kind, int n_crops, v
 int vg_vit_profile(vg_vit* v, int on);
 int vg_vit_profile_read(vg_vit* v, int32_t* h_launches, double* h_ms, double* h_flops);
 /* the same, restricted to one kernel: kind 1 = the 256 x 256 projection GEMM (k_gemm_f16_w4, or k_gemm_f16_pp64 with VG_GEMM_W4=0: every ViT-B/16
- * shape), 0 = k_gemm_f16 / k_gemm_f32, -1 = all */
+ * shape), 0 = k_gemm_f16 / k_gemm_f32, -1 = all projection GEMMs; 2 = the fp16 attention launches over all query rows, 3 = the
+ * class-row-only attention of the last block (flops: 4 * rows * T * 64 per (crop, head)) */
 int vg_vit_profile_read_kind(vg_vit* v, int kind, int32_t* h_launches, double* h_ms, double* h_flops);
 
 /* One projection GEMM of the tower, C = X @ Wt^T with the fused epilogue the block uses
@@ -132,7 +135,8 @@ int vg_gemm_resid_splitk(const void* d_X, const void* d_Wt, const float* d_bias,
 
 /* The fp16 attention kernel of the tower alone (model.py:175-187 via nn.MultiheadAttention): d_qkv fp16 [n_crops*T, ld] with
  * q | k | v at column offsets 0 | W | 2W (what in_proj writes), d_out fp16 [n_crops*T, W] = softmax(q k^T / 8) v per (crop, head).
- * Exposed so that the kernel can be unit-tested against a plain fp32 attention. */
+ * 1 <= T <= 1024: k_attention_f16 for T <= 224, the flash-style k_attention_f16_long above (ViT-L/14's 257 tokens).
+ * Exposed so that the kernels can be unit-tested against a plain fp32 attention. */
 int vg_attention(const void* d_qkv, void* d_out, int n_crops, int T, int W, int heads, int ld, void* stream);
 
 /* ---- captured classification: the hipGraph loop of BASELINE config 5 ------------------------------------------------

@@ -95,6 +95,10 @@ def main(argv=None):
                                    angle_mode=dev.get('angle_mode', 'reference'), vit_graph=bool(dev.get('vit_graph', False)),
                                    cu_reserve=int(dev.get('cu_reserve', 0)), cu_tower=dev.get('cu_tower', 'complement'))
     logger.info(f'CLIP weights: {pipeline.clip.weights_source}')
+    from vilgod_amd import clip_weights
+    tc = pipeline.clip.encoder.cfg
+    logger.info(f"CLIP tower: {clip_weights.tower_name(tc) or 'unnamed'} (width {tc['width']}, layers {tc['layers']}, patch {tc['patch']}, "
+                f"resolution {tc['resolution']}, output {tc['output_dim']})")
 
     result_path = Path(cfg.paths.results) / cfg.results_folder / '_'.join(cfg.pipeline_active)
     if rank == 0:

@@ -16,6 +16,36 @@ import numpy as np
 import torch
 
 VIT_B16 = dict(width=768, layers=12, heads=12, patch=16, resolution=224, output_dim=512)
+VIT_B32 = dict(width=768, layers=12, heads=12, patch=32, resolution=224, output_dim=512)
+VIT_L14 = dict(width=1024, layers=24, heads=16, patch=14, resolution=224, output_dim=768)
+
+# `clip.model_name` (tools/configs/preprocessor/waymo.yaml) -> the image tower the published checkpoint of that name holds
+# (clip_utils.py:19 hands the name to clip.load).  The reference's ViT-L/14@336px resamples the renderer's 224-px crops to 336 px
+# through PIL first; that resample is not implemented, so the name is refused rather than run on a different input.
+TOWERS = {
+    'ViT-B-16.pt': VIT_B16,
+    'ViT-B-32.pt': VIT_B32,
+    'ViT-L-14.pt': VIT_L14,
+}
+UNSUPPORTED_TOWERS = {
+    'ViT-L-14-336px.pt': 'ViT-L/14@336px takes 336-px crops: the renderer makes 224-px crops and the reference would resample them '
+                         'to 336 px through PIL (bicubic), which is not implemented',
+}
+
+
+def tower_name(cfg):
+    """The `TOWERS` name whose architecture `cfg` (infer_config / VitEncoder.cfg) is, or None."""
+    return next((k for k, v in TOWERS.items() if v == dict(cfg)), None)
+
+
+def tower_config(model_name):
+    """Architecture of the tower `model_name` names (a copy); None for a name not in `TOWERS` (the caller keeps ViT-B/16).
+    Raises NotImplementedError for a known tower this project cannot run."""
+    name = str(model_name)
+    if name in UNSUPPORTED_TOWERS:
+        raise NotImplementedError(f'{name}: {UNSUPPORTED_TOWERS[name]}')
+    cfg = TOWERS.get(name)
+    return dict(cfg) if cfg is not None else None
 
 
 def _gen(seed):

@@ -78,7 +78,8 @@ class VitEncoder:
 
     def profile_read(self, kind=-1):
         """-> (launches, total ms, total algorithmic FLOPs) of the projection GEMMs since profile(True);
-        kind 1: k_gemm_f16_pp64 launches only, 0: the fallback kernels only, -1: all."""
+        kind 1: k_gemm_f16_pp64 launches only, 0: the fallback kernels only, -1: all; 2 / 3: the fp16 attention launches (all rows /
+        the class-row-only last block; FLOPs 4 rows T 64 per (crop, head))."""
         n, ms, fl = ctypes.c_int32(0), ctypes.c_double(0), ctypes.c_double(0)
         check(lib.vg_vit_profile_read_kind(self._h, int(kind), ctypes.byref(n), ctypes.byref(ms), ctypes.byref(fl)),
               'vg_vit_profile_read_kind')
@@ -208,7 +209,9 @@ class ClipWrapper:
         self.template = g('prompt_template')
         class_list = list(g('class_list'))
         self.id_to_class_dict = {idx: name for idx, name in enumerate(class_list)}
-        ckpt = os.path.join(str(model_path), str(g('model_name', 'ViT-B-16.pt')))
+        model_name = str(g('model_name', 'ViT-B-16.pt'))
+        tower = clip_weights.tower_config(model_name)        # raises for ViT-L-14-336px.pt; None for a name it does not know
+        ckpt = os.path.join(str(model_path), model_name)
         if os.path.exists(ckpt):
             weights = clip_weights.load_state_dict(ckpt)
             tf_path = ckpt + '.text_features.npy'
@@ -224,9 +227,13 @@ class ClipWrapper:
             text = torch.from_numpy(np.load(tf_path) if os.path.exists(tf_path) else feats).float()
             self.weights_source = ckpt
         else:
-            weights = clip_weights.synthetic_vit_weights(synthetic_seed, **clip_weights.VIT_B16)
+            # no checkpoint on disk: seeded weights of the tower the name selects (unknown names: ViT-B/16, as always)
+            if tower is None or tower == clip_weights.VIT_B16:
+                tower, self.weights_source = clip_weights.VIT_B16, f'synthetic(seed={synthetic_seed})'
+            else:
+                self.weights_source = f'synthetic(seed={synthetic_seed}, {model_name})'
+            weights = clip_weights.synthetic_vit_weights(synthetic_seed, **tower)
             text = clip_weights.synthetic_text_features(synthetic_seed, len(class_list), weights['proj'].shape[1])
-            self.weights_source = f'synthetic(seed={synthetic_seed})'
         self.text_features = text.to(self.device).contiguous()
         self.encoder = VitEncoder(weights, dtype=dtype, device=self.device)
 

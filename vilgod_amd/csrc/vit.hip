@@ -366,14 +366,16 @@ __global__ __launch_bounds__(256) void k_gemm_f32_mfma(const float* __restrict__
 }
 
 // ---------------------------------------------------------------------------------------------
-// im2col of CHW crops into patch rows: P[(crop*G*G + py*G + px)][c*ps*ps + i*ps + j]
+// im2col of CHW crops into patch rows: P[(crop*G*G + py*G + px)][c*ps*ps + i*ps + j]; rows of Kpad >= 3*ps*ps columns (the GEMM's
+// K, a multiple of 64: 588 -> 640 for patch 14), the padding columns zero
 template <typename TI, typename TO>
-__global__ void k_im2col(const TI* __restrict__ crops, TO* __restrict__ P, int n, int res, int ps) {
+__global__ void k_im2col(const TI* __restrict__ crops, TO* __restrict__ P, int n, int res, int ps, int Kpad) {
     const int G = res / ps, Kp = 3 * ps * ps;
-    size_t total = (size_t)n * G * G * Kp;
+    size_t total = (size_t)n * G * G * Kpad;
     for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
-        int col = idx % Kp;
-        size_t row = idx / Kp;
+        int col = idx % Kpad;
+        size_t row = idx / Kpad;
+        if (col >= Kp) { P[idx] = (TO)0.f; continue; }
         int px = row % G, py = (row / G) % G;
         size_t crop = row / ((size_t)G * G);
         int j = col % ps, i = (col / ps) % ps, c = col / (ps * ps);
@@ -830,6 +832,201 @@ __global__ __launch_bounds__(448) void k_attention_f16(const f16* __restrict__ q
 #undef AT_STAMP
 }
 
+// ---------------------------------------------------------------------------------------------
+// fp16 attention, head dim 64, AT_MAXT < T <= AL_MAXT (ViT-L/14: 257 tokens) -- flash-style, the S x S scores never held at once.
+// Same MFMA layout as k_attention_f16: S^T[key][q] = K Q^T (A = K rows from LDS, B = the wave's Q fragments, in registers), so a
+// lane holds one query row's scores and the softmax is per lane (+ one cross-half shuffle); O^T[d][q] = V^T P^T with the scores
+// re-used as the B operand and V^T fragments from the transposing LDS read of row-major V (the TR path).  Online softmax over
+// 64-key blocks: running max m and running sum l per query row, O rescaled by exp2((m_old - m_new) c2) at each block.
+// Workgroup: 4 waves, one item (crop, head) at a time, persistent over items.  The item's 32-row query tiles are processed in
+// PASSES of 4 (wave w takes tile 4p + w); every pass streams the item's K / V through two LDS buffers of 64 keys (register-staged:
+// the next block's loads are in flight under this block's MFMAs and softmax, written to the other buffer behind them, one barrier
+// per block).  The step sequence (item, pass, key block) is flat, so the prefetch runs across pass and item seams too.
+// Load balance: 257 tokens = 8 x 32 + 1 -> 9 tiles -> passes of 4, 4 and 1 tiles: in the third pass waves 1-3 only stage K / V and
+// wait at the barriers (their SIMDs serve the CU's other workgroup meanwhile), and tile 8 computes 32 rows for its one live row.
+// 9 of 12 wave-passes compute; K / V are read three times per item, from L2 after the first.  (Tiles per pass for other T:
+// 225 -> 8 = 4 + 4; 577 -> 19 = 5 passes, last 3 of 4; 1024 -> 32 = 8 full passes.)
+// Keys >= T: the last block's rows beyond T are staged as zeros (a clamped row's load, replaced by zero when written to LDS), their
+// scores are set to -inf before the max, and 16-key steps wholly beyond T skip their P V MFMAs.
+// q_tiles: query tiles wanted (1 in the class-row-only last block).  A tile's arithmetic does not depend on the other tiles, so the
+// class row is bit-identical to an all-rows launch.  LDS: 2 x (K + V) 64-key images + a 32-row output tile per wave = 55,296 B,
+// two workgroups per CU.
+#define AL_MAXT 1024
+#define AL_KB 64
+#define AL_BUF (AL_KB * AT_KLD)                                       // halves of one 64-key K (or V) image
+#define AL_LDS_BYTES ((4 * AL_BUF + 4 * 32 * AT_KLD) * 2)            // 55,296 B
+__global__ __launch_bounds__(256, 2) void k_attention_f16_long(const f16* __restrict__ qkv, f16* __restrict__ out, int T, int W,
+                                                               int heads, int ld, int n_items, int q_tiles) {
+    extern __shared__ __attribute__((aligned(16))) char al_smem[];   // [buffer 0: K | V][buffer 1: K | V][wave 0..3 output tile]
+    f16* const KV = (f16*)al_smem;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    f16* const Os = KV + 4 * AL_BUF + wave * 32 * AT_KLD;
+    const int r31 = lane & 31, hh = lane >> 5;
+    const int crow = lane >> 3, cpart = lane & 7;
+    const int tr_i = lane & 15, tr_g = lane >> 4;
+    const int tr_off = ((4 * (tr_g >> 1) + (tr_i >> 2)) * AT_KLD + 16 * (tr_g & 1) + 4 * (tr_i & 3)) * 2;
+    const int ntile = (T + 31) / 32;
+    const int qt = q_tiles < ntile ? q_tiles : ntile;
+    const int npass = (qt + 3) / 4;
+    const int nkb = (T + AL_KB - 1) / AL_KB;
+    const int per_item = npass * nkb;
+    const int my_items = (int)blockIdx.x < n_items ? (n_items - 1 - (int)blockIdx.x) / (int)gridDim.x + 1 : 0;
+    const int nsteps = my_items * per_item;
+    if (nsteps == 0) return;                                          // (workgroup-uniform, before any barrier)
+    // step s -> (item, pass, key block); all wave-uniform
+    auto decode = [&](int s, int& item, int& pass, int& kb) {
+        const int u = s / per_item, r = s - u * per_item;
+        item = (int)blockIdx.x + u * (int)gridDim.x;
+        pass = r / nkb;
+        kb = r - pass * nkb;
+    };
+    uint4 kreg[2];
+    f16x8 vreg[2], qn[4];
+    // 64 keys x 128 B of K and of V per block: 512 16-byte parts each, thread tid takes parts tid and tid + 256 of both
+    auto fetch = [&](int s) {
+        int item, pass, kb;
+        decode(s, item, pass, kb);
+        const int crop = item / heads, head = item - crop * heads;
+        const f16* base = qkv + (size_t)crop * T * ld + head * 64;
+#pragma unroll
+        for (int it = 0; it < 2; ++it) {
+            const int c = tid + it * 256, key = kb * AL_KB + (c >> 3), part = c & 7;
+            const unsigned off = (unsigned)((key < T ? key : T - 1) * ld + part * 8);
+            kreg[it] = *(const uint4*)(base + W + off);
+            vreg[it] = *(const f16x8*)(base + 2 * W + off);
+        }
+        if (kb == 0) {                                                // the pass's Q fragments: row (4 pass + wave) * 32 + r31, clamped
+            const int qr = (pass * 4 + wave) * 32 + r31;
+            const unsigned off = (unsigned)((qr < T ? qr : T - 1) * ld + hh * 8);
+#pragma unroll
+            for (int s4 = 0; s4 < 4; ++s4) qn[s4] = *(const f16x8*)(base + off + s4 * 16);
+        }
+    };
+    auto stage = [&](int s) {
+        int item, pass, kb;
+        decode(s, item, pass, kb);
+        f16* const Kb = KV + (s & 1) * 2 * AL_BUF;
+        f16* const Vb = Kb + AL_BUF;
+        const f16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+        for (int it = 0; it < 2; ++it) {
+            const int c = tid + it * 256, row = c >> 3, part = c & 7;
+            const bool live = kb * AL_KB + row < T;
+            *(uint4*)(Kb + row * AT_KLD + part * 8) = live ? kreg[it] : make_uint4(0, 0, 0, 0);
+            *(f16x8*)(Vb + row * AT_KLD + part * 8) = live ? vreg[it] : z;
+        }
+    };
+    fetch(0);
+    stage(0);
+    __syncthreads();
+    const float c2 = 0.125f * 1.4426950408889634f;                   // dh^-0.5 in log2 units
+    f16x8 qf[4];
+    f32x16 oacc[2];
+    float m = -INFINITY, l = 0.f;
+    for (int s = 0; s < nsteps; ++s) {
+        int item, pass, kb;
+        decode(s, item, pass, kb);
+        if (kb == 0) {
+#pragma unroll
+            for (int s4 = 0; s4 < 4; ++s4) qf[s4] = qn[s4];
+#pragma unroll
+            for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) oacc[dt][r] = 0.f;
+            m = -INFINITY;
+            l = 0.f;
+        }
+        if (s + 1 < nsteps) fetch(s + 1);                              // in flight during the compute below
+        const int tile = pass * 4 + wave;
+        if (tile < qt) {
+            const f16* const Kb = KV + (s & 1) * 2 * AL_BUF;
+            const f16* const Vb = Kb + AL_BUF;
+            f32x16 sacc[2];
+#pragma unroll
+            for (int h2 = 0; h2 < 2; ++h2) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) sacc[h2][r] = 0.f;
+#pragma unroll
+                for (int s4 = 0; s4 < 4; ++s4) {
+                    const f16x8 kf = *(const f16x8*)(Kb + (h2 * 32 + r31) * AT_KLD + s4 * 16 + hh * 8);
+                    sacc[h2] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[s4], sacc[h2], 0, 0, 0);
+                }
+            }
+            const int k0 = kb * AL_KB;
+            if (k0 + AL_KB > T) {                                      // the last block: keys >= T out of the max and the sum
+#pragma unroll
+                for (int h2 = 0; h2 < 2; ++h2)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r)
+                        if (k0 + h2 * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh >= T) sacc[h2][r] = -INFINITY;
+            }
+            float mx = m;
+#pragma unroll
+            for (int h2 = 0; h2 < 2; ++h2)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) mx = fmaxf(mx, sacc[h2][r]);
+            mx = fmaxf(mx, __shfl_xor(mx, 32));                        // finite: key k0 < T is in every block
+            const float alpha = __builtin_amdgcn_exp2f((m - mx) * c2); // exp2(-inf) = 0 at the first block
+            m = mx;
+            const float mc = -mx * c2;
+            float ps = 0.f;
+#pragma unroll
+            for (int h2 = 0; h2 < 2; ++h2)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const float p = __builtin_amdgcn_exp2f(fmaf(sacc[h2][r], c2, mc));
+                    sacc[h2][r] = p;
+                    ps += p;
+                }
+            l = fmaf(l, alpha, ps);                                    // this lane's keys; the halves are added at the end
+#pragma unroll
+            for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) oacc[dt][r] *= alpha;
+#pragma unroll
+            for (int h2 = 0; h2 < 2; ++h2)
+#pragma unroll
+                for (int s2 = 0; s2 < 2; ++s2) {
+                    if (k0 + h2 * 32 + 16 * s2 >= T) continue;         // 16 keys that do not exist (wave-uniform)
+                    f16x8 pf;
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) pf[j] = (f16)sacc[h2][8 * s2 + j];
+#pragma unroll
+                    for (int dt = 0; dt < 2; ++dt) {
+                        // A[d][k]: element j <-> key k0 + 32 h2 + 16 s2 + 8(j>>2) + 4hh + (j&3)
+                        const char* vb = (const char*)Vb + tr_off + ((h2 * 32 + 16 * s2) * AT_KLD + dt * 32) * 2;
+                        const f16x4 lo = __builtin_bit_cast(f16x4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4v*)vb));
+                        const f16x4 hi = __builtin_bit_cast(f16x4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4v*)(vb + 8 * AT_KLD * 2)));
+                        const f16x8 vf = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+                        oacc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, pf, oacc[dt], 0, 0, 0);
+                    }
+                }
+            if (kb == nkb - 1) {                                       // the pass's last block: O / l -> rows through the wave's tile
+                const float inv = 1.0f / (l + __shfl_xor(l, 32));
+#pragma unroll
+                for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+                    for (int g = 0; g < 4; ++g) {
+                        f16x4 h4;
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) h4[e] = (f16)(oacc[dt][4 * g + e] * inv);
+                        *(f16x4*)(Os + r31 * AT_KLD + dt * 32 + 8 * g + 4 * hh) = h4;
+                    }
+                const int crop = item / heads, head = item - crop * heads;
+                f16* const obase = out + (size_t)crop * T * W + head * 64;
+#pragma unroll
+                for (int it = 0; it < 4; ++it) {
+                    const int qr = tile * 32 + it * 8 + crow;
+                    const f16x8 v = *(const f16x8*)(Os + (it * 8 + crow) * AT_KLD + cpart * 8);
+                    if (qr < T) *(f16x8*)(obase + (size_t)qr * W + cpart * 8) = v;
+                }
+            }
+        }
+        if (s + 1 < nsteps) stage(s + 1);                              // the other buffer: every wave left it at the last barrier
+        __syncthreads();
+    }
+}
+
 // Measured and dropped (round 4): k_attention_f16_dma -- K and V double-buffered in LDS and filled by LDS-DMA (8-row x 128-byte pieces,
 // chunk swizzle by the reversed bits of row >> 1: conflict-free for the K fragment reads and the transposing V reads), the next item
 // requested under this item's MFMAs and softmax, no staging phase, one barrier per item, 207 instead of 249 VGPRs.  Two things the
@@ -1030,7 +1227,7 @@ struct vg_vit {
     int prof_on = 0, prof_n = 0;
     hipEvent_t prof_ev[2 * VG_PROF_MAX];
     double prof_flops[VG_PROF_MAX];
-    int prof_kind[VG_PROF_MAX];      // 0 = k_gemm_f16 / k_gemm_f32, 1 = k_gemm_f16_pp64 / pp16
+    int prof_kind[VG_PROF_MAX];      // 0 = k_gemm_f16 / k_gemm_f32, 1 = k_gemm_f16_pp64 / pp16, 2 / 3 = fp16 attention (all rows / class rows)
     bool prof_init = false;
     std::map<std::string, void*> w;        // device pointers (f32 or f16 depending on role)
     std::map<std::string, size_t> numel;
@@ -1056,6 +1253,10 @@ static bool is_gemm_weight(const std::string& n) {
            n.find("out_proj.weight") != std::string::npos || n.find("c_fc.weight") != std::string::npos ||
            n.find("c_proj.weight") != std::string::npos;
 }
+
+// K of the patch-embedding GEMM: 3 * patch^2 rounded up to a multiple of 64 (ViT-L/14: 588 -> 640; patch 16 / 32: unpadded).  The
+// im2col rows and conv1.weight's rows carry zero columns up to it.
+static int vit_kpad(const vg_vit* v) { return (3 * v->patch * v->patch + 63) / 64 * 64; }
 
 // column tiles per L2 chunk: the largest divisor-friendly count whose weight rows (128*K fp16 each) fit ~2.4 MB
 static int gemm_chunk_tiles(int N, int K) {
@@ -2101,6 +2302,17 @@ static int launch_gemm(const vg_vit* cv, const void* X, const void* Wt, const fl
 template <bool TRACE>
 static int launch_attention(const f16* qkv, f16* out, int T, int W, int heads, int ld, int items, long long* trace, hipStream_t st,
                             int q_tiles = 7, bool tr = true, bool stagger = true) {
+    if (T > AT_MAXT && !TRACE) {                 // ViT-L/14 and other long token counts: the flash-style kernel
+        if (T > AL_MAXT) return VG_ERR_ARG;
+        static std::atomic<int> n_cu_{0};
+        int n_cu = n_cu_.load();
+        if (!n_cu) { int dev = 0; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev); if (n_cu < 8) n_cu = 256; n_cu_.store(n_cu); }
+        const dim3 grid(items < 2 * n_cu ? items : 2 * n_cu);     // persistent: two workgroups per CU
+        VG_MAX_DYNAMIC_LDS(k_attention_f16_long, AL_LDS_BYTES);
+        hipLaunchKernelGGL(k_attention_f16_long, grid, dim3(256), AL_LDS_BYTES, st, qkv, out, T, W, heads, ld, items, q_tiles);
+        VG_LAUNCH_CHECK();
+        return VG_OK;
+    }
     const int nkb = (T + 31) / 32;
     if (nkb < 1 || nkb > 7) return VG_ERR_ARG;
     // ViT-B/16: row-major V + transposing LDS reads (VG_ATT_TR=0: the transposed V image of rounds 1-2; same numbers, 1.6 % slower)
@@ -2280,7 +2492,9 @@ int vg_vit_create(vg_vit** out, int width, int layers, int heads, int patch, int
     if (!out || width % 128 || width > 1024 || heads * 64 != width || resolution % patch || dtype < 0 || dtype > 1)
         return VG_ERR_ARG;
     int T = (resolution / patch) * (resolution / patch) + 1;
-    if (T > AT_MAXT || (3 * patch * patch) % 64) return VG_ERR_ARG;
+    // f16: k_attention_f16 up to AT_MAXT tokens, k_attention_f16_long up to AL_MAXT; f32: k_attention_f32 keeps an item's K, V and
+    // four rows of probabilities per wave in LDS, (T * 65 + T * 64 + 16 * T) * 4 bytes within the 160 KiB it requests (T <= 282)
+    if (dtype == 1 ? T > AL_MAXT : (size_t)T * (65 + 64 + 16) * 4 > 160 * 1024) return VG_ERR_ARG;
     vg_vit* v = new vg_vit();
     v->width = width; v->layers = layers; v->heads = heads; v->patch = patch; v->res = resolution;
     v->out_dim = out_dim; v->dtype = dtype; v->T = T;
@@ -2341,6 +2555,15 @@ int vg_vit_set_weight(vg_vit* v, const char* name, const float* h_data, int64_t 
             v->w32[n] = d32;
         }
     }
+    std::vector<float> padded;
+    if (n == "conv1.weight" && vit_kpad(v) != 3 * v->patch * v->patch) {     // [W, 3 p^2] -> [W, Kpad] with zero columns
+        const int K = 3 * v->patch * v->patch, Kp = vit_kpad(v);
+        if (numel != (int64_t)v->width * K) return VG_ERR_ARG;
+        padded.assign((size_t)v->width * Kp, 0.f);
+        for (int r = 0; r < v->width; ++r) memcpy(padded.data() + (size_t)r * Kp, h_data + (size_t)r * K, (size_t)K * 4);
+        h_data = padded.data();
+        numel = (int64_t)padded.size();
+    }
     void* d = nullptr;
     if (v->dtype == 1 && is_gemm_weight(n)) {
         std::vector<f16> tmp((size_t)numel);
@@ -2391,7 +2614,7 @@ static int64_t pad128(int64_t m) { return (m + 255) / 256 * 256; }   // GEMM row
 int64_t vg_vit_workspace_bytes(const vg_vit* v, int n_crops) {
     if (!v || n_crops <= 0) return 0;
     int64_t Mp = pad128((int64_t)n_crops * v->T), W = v->width, es = v->dtype == 1 ? 2 : 4;
-    int64_t Pp = pad128((int64_t)n_crops * (v->T - 1)), Kp = 3 * v->patch * v->patch;
+    int64_t Pp = pad128((int64_t)n_crops * (v->T - 1)), Kp = vit_kpad(v);
     int64_t b = Mp * W * 4            // x (f32)
                 + Mp * W * es         // h
                 + Mp * (3 * W + 256) * es   // qkv (padded row stride)
@@ -2408,10 +2631,11 @@ int vg_vit_encode(vg_vit* v, const void* d_crops, int input_kind, int n_crops, v
     if (!v || !d_crops || !d_workspace || !d_feat || n_crops <= 0 || input_kind < 0 || input_kind > 3) return VG_ERR_ARG;
     if (input_kind >= 2 && v->dtype != 1) return VG_ERR_ARG;
     if (input_kind == 3 && (v->patch * v->patch) % 128) return VG_ERR_ARG;       // K of the folded patch embedding: two 64-wide K-tiles at least
+    if (input_kind == 2 && vit_kpad(v) != 3 * v->patch * v->patch) return VG_ERR_ARG; // renderer patch rows carry no K padding
     hipStream_t st = (hipStream_t)stream;
     const int W = v->width, T = v->T, L = v->layers, H = v->heads;
     const int64_t M = (int64_t)n_crops * T, Mp = pad128(M), es = v->dtype == 1 ? 2 : 4;
-    const int64_t P = (int64_t)n_crops * (T - 1), Pp = pad128(P), Kp = 3 * v->patch * v->patch;
+    const int64_t P = (int64_t)n_crops * (T - 1), Pp = pad128(P), Kp = vit_kpad(v);     // patch-embedding K, padded to 64
     char* ws = (char*)d_workspace;
     float* x = (float*)ws;            ws += Mp * W * 4;
     void* h = ws;                     ws += Mp * W * es;
@@ -2448,14 +2672,14 @@ int vg_vit_encode(vg_vit* v, const void* d_crops, int input_kind, int n_crops, v
         if (blocks > 65535 * 8) blocks = 65535 * 8;
         if (v->dtype == 1) {
             if (input_kind == 0)
-                hipLaunchKernelGGL((k_im2col<float, f16>), dim3(blocks), dim3(256), 0, st, (const float*)d_crops, (f16*)patches, n_crops, v->res, v->patch);
+                hipLaunchKernelGGL((k_im2col<float, f16>), dim3(blocks), dim3(256), 0, st, (const float*)d_crops, (f16*)patches, n_crops, v->res, v->patch, (int)Kp);
             else
-                hipLaunchKernelGGL((k_im2col<f16, f16>), dim3(blocks), dim3(256), 0, st, (const f16*)d_crops, (f16*)patches, n_crops, v->res, v->patch);
+                hipLaunchKernelGGL((k_im2col<f16, f16>), dim3(blocks), dim3(256), 0, st, (const f16*)d_crops, (f16*)patches, n_crops, v->res, v->patch, (int)Kp);
         } else {
             if (input_kind == 0)
-                hipLaunchKernelGGL((k_im2col<float, float>), dim3(blocks), dim3(256), 0, st, (const float*)d_crops, (float*)patches, n_crops, v->res, v->patch);
+                hipLaunchKernelGGL((k_im2col<float, float>), dim3(blocks), dim3(256), 0, st, (const float*)d_crops, (float*)patches, n_crops, v->res, v->patch, (int)Kp);
             else
-                hipLaunchKernelGGL((k_im2col<f16, float>), dim3(blocks), dim3(256), 0, st, (const f16*)d_crops, (float*)patches, n_crops, v->res, v->patch);
+                hipLaunchKernelGGL((k_im2col<f16, float>), dim3(blocks), dim3(256), 0, st, (const f16*)d_crops, (float*)patches, n_crops, v->res, v->patch, (int)Kp);
         }
         VG_LAUNCH_CHECK();
     }
@@ -2557,8 +2781,16 @@ int vg_vit_encode(vg_vit* v, const void* d_crops, int input_kind, int n_crops, v
         if (rc) return rc;
         if (v->dtype == 1) {
             {
-                rc = launch_attention<false>((const f16*)qkv, (f16*)h, T, W, H, qkv_ld, n_crops * H, nullptr, st, cls_only ? 1 : 7, v->att_tr, v->att_stagger);
+                // measurement hook (vg_vit_profile_read_kind 2 / 3): an event pair around each attention launch
+                const bool aprof = v->prof_on && v->prof_n < VG_PROF_MAX;
+                if (aprof) (void)hipEventRecord(v->prof_ev[2 * v->prof_n], st);
+                rc = launch_attention<false>((const f16*)qkv, (f16*)h, T, W, H, qkv_ld, n_crops * H, nullptr, st, cls_only ? 1 : (T + 31) / 32, v->att_tr, v->att_stagger);
                 if (rc) return rc;
+                if (aprof) {
+                    (void)hipEventRecord(v->prof_ev[2 * v->prof_n + 1], st);
+                    v->prof_kind[v->prof_n] = cls_only ? 3 : 2;
+                    v->prof_flops[v->prof_n++] = 4.0 * (cls_only ? 1.0 : (double)T) * (double)T * 64.0 * (double)(n_crops * H);
+                }
             }
         } else {
             size_t lds = ((size_t)T * 65 + (size_t)T * 64 + 16 * (size_t)T) * sizeof(float);
@@ -2631,10 +2863,10 @@ int vg_vit_encode(vg_vit* v, const void* d_crops, int input_kind, int n_crops, v
 /* k_attention_f16 alone: softmax(q k^T / 8) v per (crop, head) on the padded qkv rows in_proj writes (model.py:175-187 via
  * nn.MultiheadAttention); exposed so that the kernel can be unit-tested against a plain fp32 attention. */
 int vg_attention(const void* d_qkv, void* d_out, int n_crops, int T, int W, int heads, int ld, void* stream) {
-    if (!d_qkv || !d_out || n_crops <= 0 || T > AT_MAXT || heads * 64 != W) return VG_ERR_ARG;
+    if (!d_qkv || !d_out || n_crops <= 0 || T < 1 || T > AL_MAXT || heads * 64 != W) return VG_ERR_ARG;
     const char* tr_env = getenv("VG_ATT_TR");           // handle-less test entry point: read per call, on the caller's thread
     const char* sg_env = getenv("VG_ATT_STAGGER");
-    return launch_attention<false>((const f16*)d_qkv, (f16*)d_out, T, W, heads, ld, n_crops * heads, nullptr, (hipStream_t)stream, 7,
+    return launch_attention<false>((const f16*)d_qkv, (f16*)d_out, T, W, heads, ld, n_crops * heads, nullptr, (hipStream_t)stream, (T + 31) / 32,
                                    !(tr_env && atoi(tr_env) == 0), !(sg_env && atoi(sg_env) == 0));
 }
 
@@ -2692,7 +2924,7 @@ int vg_vit_profile_read_kind(vg_vit* v, int kind, int32_t* h_launches, double* h
     if (!v || !h_launches || !h_ms || !h_flops) return VG_ERR_ARG;
     *h_launches = 0; *h_ms = 0; *h_flops = 0;
     for (int i = 0; i < v->prof_n; ++i) {
-        if (kind >= 0 && v->prof_kind[i] != kind) continue;
+        if (kind >= 0 ? v->prof_kind[i] != kind : v->prof_kind[i] >= 2) continue;     // (-1: the projection GEMMs)
         VG_CHECK(hipEventSynchronize(v->prof_ev[2 * i + 1]));
         float ms = 0.f;
         VG_CHECK(hipEventElapsedTime(&ms, v->prof_ev[2 * i], v->prof_ev[2 * i + 1]));

@@ -475,24 +475,31 @@ class PseudoLabelPipeline:
                 return probs.clone(), top1.clone(), score.clone()
             patches = self.projection.render_frame(d_X, d_index, d_seg, transform_to_ego, out=pmode)
             self._mark('render')
-            vs = self.vit_stream
-            if vs is None or n == 0:
-                with self._vit_in_turn():
-                    return clip_scores(enc.encode_patches(patches, n), self.clip.text_features)
-            # CU-masked streams: the tower runs on this worker's ViT stream (its own CU set), ordered after the render and in front of
-            # whatever this frame's stream does next
-            cur = torch.cuda.current_stream(self.device)
-            vs.wait_stream(cur)
-            patches.record_stream(vs)
-            with torch.cuda.stream(vs):
-                with self._vit_in_turn():
-                    out = clip_scores(enc.encode_patches(patches, n), self.clip.text_features)
-            cur.wait_stream(vs)
-            for t_ in out:
-                t_.record_stream(cur)
-            return out
+            return self._on_vit_stream(lambda: clip_scores(enc.encode_patches(patches, n), self.clip.text_features), patches, n)
         crops = self.projection.render_frame(d_X, d_index, d_seg, transform_to_ego, out='f16' if self.vit_dtype == 'f16' else 'f32')
-        return self.clip.predict_probs(crops)
+        if enc.cfg['patch'] == 16:
+            return self.clip.predict_probs(crops)
+        # other towers (ViT-B/32, ViT-L/14: CHW crops, im2col in the tower) take the patch-16 path's CU-masked stream and frames-in-flight turn
+        return self._on_vit_stream(lambda: self.clip.predict_probs(crops), crops, n)
+
+    def _on_vit_stream(self, run, inp, n):
+        """run() -> (probs, top1, score) under the frames-in-flight turn, on this worker's ViT stream when it has one."""
+        vs = self.vit_stream
+        if vs is None or n == 0:
+            with self._vit_in_turn():
+                return run()
+        # CU-masked streams: the tower runs on this worker's ViT stream (its own CU set), ordered after the render and in front of
+        # whatever this frame's stream does next
+        cur = torch.cuda.current_stream(self.device)
+        vs.wait_stream(cur)
+        inp.record_stream(vs)
+        with torch.cuda.stream(vs):
+            with self._vit_in_turn():
+                out = run()
+        cur.wait_stream(vs)
+        for t_ in out:
+            t_.record_stream(cur)
+        return out
 
     @contextlib.contextmanager
     def _vit_in_turn(self):
