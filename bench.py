@@ -33,13 +33,16 @@ median block's time / its steps): one 0.3 s window on a shared box reads +-4 %. 
 returned (result dict, FrameState arrays, score matrix) as DIR/<name>.npy after the timed steps: the inputs are seeded, so two builds
 run with the same arguments can be compared output for output.
 
-The JSON line also carries
+A plain run does only what the metric needs: set-up, warm-up, the timed steps, `--dump-outputs`, the JSON line.  Everything else
+runs after the timed steps and only with `--full` (the `--no-*` switches below then leave out single parts of it).  With `--full`
+the JSON line also carries
   roofline      the dominant kernel (the ViT projection GEMM): algorithmic FLOPs / launch duration, measured live with HIP
-                event pairs on the launch stream (csrc/vit.hip vg_vit_profile), vs the dense fp16 MFMA peak of
-                /opt/skills/guides/MI355X_MICROARCH.md
+                event pairs on the launch stream (csrc/vit.hip vg_vit_profile), vs the dense fp16 MFMA peak of the MI355X
+                (PEAK_F16_MFMA_TFLOPS); tower_two_in_flight and frame_latency_ms beside it
   cpu_baseline  the CPU oracle (oracle/pipeline_oracle.py, kind "port": the reference cannot travel to the GPU box) timed on a
                 bounded sample of the metric's workload on the host cores of the same box (rank 0, N=1 only)
 and, as information beside the metric (N=1 only; each block reports its own failure instead of costing the metric line):
+  multi_gpu_model      what frame sharding costs, modelled and emulated as rank 0 of N on this one GPU
   box_modes            the same frames with box_mode 'fast' (GPU hull, all edges) next to the default 'reference' mode
   resident_input       the same frames uploaded to HBM before the clock starts (what rounds 1-2 quoted as the metric)
   resid16              the same frames with the fp16 residual stream of the reference's own GPU run (VG_VIT_RESID16=1) beside the default fp32 stream
@@ -226,6 +229,8 @@ def main():
     ap.add_argument('--emulate-world', type=int, nargs='*', default=[2, 4, 8],
                     help='N = 1 only: world sizes whose rank 0 this one GPU emulates inside the multi_gpu_model block (all N K uploads + ground '
                          'passes of the replicated round-robin design, K own frames); empty = skip')
+    ap.add_argument('--full', action='store_true', help='after the timed steps, also measure everything beside the metric: roofline pass, frame latency, '
+                    'information blocks, reference stage order, cli_mode, CPU baseline (off: the run does only what the metric line needs)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-extras', action='store_true', help='skip the information blocks beside the metric (box_modes, views6, dense200k, cli_mode)')
     ap.add_argument('--cli-frames', type=int, default=199, help='frames of the synthetic sequence of the cli_mode block')
@@ -477,7 +482,8 @@ def main():
     # that the live average and the rocprofv3 kernel-trace average are taken over the same launches (the average launch time follows
     # the frame's crop count)
     n_pass = min(6, W + K)
-    if not args.no_roofline_pass:
+    roofline_pass = args.full and not args.no_roofline_pass
+    if roofline_pass:
         pipe.clip.encoder.profile(True)
         for i in range(n_pass):
             pipe.process_frame(pipe.upload(frames[i]), poses[i + 1], poses[0], fnr=i)
@@ -489,7 +495,7 @@ def main():
     # every stage; medians over six frames after two untimed ones).  Not a throughput figure: it is what an online user waits for, and what a
     # timed block pays once while its pipeline fills (the first frame's front stage runs on an empty GPU before the first GEMM starts).
     frame_latency = None
-    if not args.no_roofline_pass and not args.stage_times and world == 1:
+    if roofline_pass and not args.stage_times and world == 1:
         rows_l = []
         pipe.new_sequence()
         for i in range(min(8, W + K)):
@@ -510,7 +516,7 @@ def main():
     # are 257 row tiles x 3 column tiles = 3.01 rounds of 256 CUs for out_proj / c_proj); two encodes in flight fill each other's tails,
     # which is what the timed region sees (tools/exp_tile_tail.py: 40.4 us per crop whatever the crop count, against 42-46 with one).
     tower2 = None
-    if not args.no_roofline_pass and not args.stage_times and args.dtype == 'f16':
+    if roofline_pass and not args.stage_times and args.dtype == 'f16':
         import threading
         n_cr = int(round(sum(p_.shape[0] for _, _, p_ in outs) / max(len(outs), 1))) or 337
         rows2 = (n_cr * 196 + 255) // 256 * 256
@@ -547,7 +553,7 @@ def main():
         achieved = gemm_flops / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else 0.0
         traffic = traffic_src = by_kind = pmc_mfma = None
         tpath = os.path.join(ROOT, 'profiles', 'gemm_traffic.json')       # tools/collect_profiles.sh + summarize_profiles.py
-        if os.path.exists(tpath):
+        if args.full and os.path.exists(tpath):
             tj = json.load(open(tpath))
             traffic = round(tj['hbm_bytes_per_launch'])
             by_kind, pmc_mfma = tj.get('by_kind') or None, tj.get('mfma_utilisation')
@@ -586,7 +592,9 @@ def main():
                 'weights': pipe.clip.weights_source, 'parallelism': f'frame-sharded x{world}', 'frames_in_flight_per_gpu': inflight, 'vit_passes_at_a_time': int(os.environ.get('VILGOD_VIT_CONCURRENCY', '3')),
                 'box_mode': args.box_mode,
             },
-            'roofline': {
+        }
+        if args.full:
+            out['roofline'] = {
                 'kernel': f'{DOMINANT_KERNEL} (every ViT projection GEMM: in_proj, out_proj, c_fc, c_proj, patch embedding)',
                 'bound': 'mfma', 'achieved': round(achieved, 1), 'peak': PEAK_F16_MFMA_TFLOPS, 'unit': 'TFLOP/s',
                 'frac': round(achieved / PEAK_F16_MFMA_TFLOPS, 4), 'traffic': traffic, 'traffic_unit': 'HBM bytes per launch (PMC)',
@@ -604,8 +612,7 @@ def main():
                 'all_projection_gemms': {'launches': all_launches,
                                          'achieved': round(all_flops / (all_ms * 1e-3) / 1e12, 1) if all_ms > 0 else 0.0,
                                          'ms_per_frame': round(all_ms / max(n_pass, 1), 3)},
-            },
-        }
+            }
         # scalars inside `config` / `roofline` (a record that keeps only scalar keys of those two still carries the evidence; VERDICT r5 task 5)
         bvals, bcrops = out['block_values'], out['block_crops_per_frame']
         for i, (bv, bc) in enumerate(zip(bvals, bcrops)):
@@ -625,7 +632,7 @@ def main():
             out['roofline']['front_stage_latency_ms'] = frame_latency['front_stage_until_the_crops_are_queued']
         if args.stage_times:
             out['stage_ms_per_frame'] = {k: round(1000.0 * v / K, 3) for k, v in stage.items()}
-        if world == 1 and not args.stage_times and not args.no_extras:
+        if args.full and world == 1 and not args.stage_times and not args.no_extras:
             def multi_gpu_model():
                 # what frame sharding costs, from this GPU's own numbers (no multi-GPU node is available to the builder; the driver's
                 # SCALE file is the measurement): t_f = this run's ms per step, t_g = a ground pass (upload + kernels) timed back to back in
@@ -705,7 +712,7 @@ def main():
                 out['multi_gpu_model'] = {'error': f'{type(e).__name__}: {e}'}
             for n_, rec in ((out['multi_gpu_model'].get('measured_single_rank_emulation') or {}).items()):
                 out['config'][f'rank0_of_{n_}_efficiency_measured'] = rec['replicate_efficiency_measured']      # (scalar copies, see above)
-        extras = world == 1 and not args.no_extras and not args.stage_times
+        extras = args.full and world == 1 and not args.no_extras and not args.stage_times
 
         def block(name, fn):
             """An information block must never cost the metric line: failures are reported inside the JSON."""
@@ -927,7 +934,7 @@ def main():
             block('roofline_stages', roofline_stages)
             block('views6', shape_block(args.points, args.objects, 6, 'BASELINE config 3 as written: 150k points, 6 rendered views'))
             block('dense200k', shape_block(200_000, 120, args.views, 'BASELINE config 5 shape: dense 200k-point frames, ~120 objects, fp16 ViT'))
-        if world == 1 and not args.no_sequence_pass and not args.stage_times:
+        if args.full and world == 1 and not args.no_sequence_pass and not args.stage_times:
             def default_config_mode():
                 # the reference's DEFAULT stage order (preprocessing.yaml:50-68 -- entropy scores over a 15-frame window + two-frame
                 # 5-D clustering) on one coherent synthetic sequence, as a library call
@@ -1008,7 +1015,7 @@ def main():
                                      'that run on a thread under the next sequence\'s GPU stages; whole_command_seconds adds start-up, the generator and '
                                      'the AP evaluation over the generator\'s ground truth')}
             block('cli_mode', cli_mode)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             block('cpu_baseline', cpu_baseline)
         print(json.dumps(out), flush=True)
     if dist is not None:

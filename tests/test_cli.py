@@ -282,7 +282,7 @@ def test_bench_two_ranks_on_one_gpu(cuda, handoff):
     import json
     env = dict(os.environ, MASTER_ADDR='127.0.0.1', MASTER_PORT=_free_port(), WORLD_SIZE='2', VILGOD_DIST_BACKEND='gloo')
     cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1', '--points', '30000',
-           '--objects', '12', '--no-cpu-baseline', '--no-sequence-pass', '--no-extras', '--ground-handoff', handoff]
+           '--objects', '12', '--full', '--no-cpu-baseline', '--no-sequence-pass', '--no-extras', '--ground-handoff', handoff]
     import tempfile
     tmp = tempfile.mkdtemp()
     files = [(open(f'{tmp}/o{k}', 'w'), open(f'{tmp}/e{k}', 'w')) for k in range(2)]
@@ -300,6 +300,24 @@ def test_bench_two_ranks_on_one_gpu(cuda, handoff):
     assert d['n_gpus'] == 2 and d['steps'] == 3 and d['scaling'] == 'weak' and d['value'] > 0 and d['unit'] == 'frames/s'
     assert d['value'] == pytest.approx(2 * 3 / (d['ms_per_step'] * 3 / 1000.0), rel=1e-3)       # whole-job frames / max-rank time
     assert 0 < d['roofline']['frac'] < 1 and 'cpu_baseline' not in d
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_prints_the_metric_only(cuda, tmp_path):
+    """Without --full, bench.py sets up, warms up, times the steps, dumps the last step and prints the metric line: no roofline
+    pass, information blocks or CPU baseline after the timed steps."""
+    import json
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '2', '--warmup', '1', '--points', '30000',
+                        '--objects', '12', '--dump-outputs', str(tmp_path / 'out')], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d['n_gpus'] == 1 and d['steps'] == 2 and d['unit'] == 'frames/s' and d['higher_is_better'] and d['dtype'] == 'f16'
+    assert d['value'] == pytest.approx(2 / (d['ms_per_step'] * 2 / 1000.0), rel=1e-3)
+    moved = {'roofline', 'frame_latency_ms', 'multi_gpu_model', 'box_modes', 'resident_input', 'cli_mode', 'default_config_mode', 'cpu_baseline'}
+    assert not moved & set(d)
+    assert (tmp_path / 'out' / 'crop_probs.npy').exists() and (tmp_path / 'out' / 'boxes_lidar.npy').exists()
 
 
 @pytest.mark.gpu
