@@ -123,6 +123,23 @@ int vg_vit_profile_read_kind(vg_vit* v, int kind, int32_t* h_launches, double* h
 int vg_gemm(int dtype, int epi, const void* d_X, const void* d_Wt, const float* d_bias, void* d_C, float* d_resid,
             int M, int N, int K, void* stream);
 
+/* The folded-LayerNorm epilogues of the fp16 projection GEMM (model.py:190-191: ln_1 / ln_2 ride in in_proj / c_fc), alone, for
+ * unit tests.  Handle-less like vg_gemm: the kernel family is chosen by VG_GEMM_W4, read per call.  d_X, d_Wt f16; M % 256 == 0,
+ * N % 256 == 0, K % 64 == 0, K >= 256 under k_gemm_f16_w4.  d_stats: LnPartial[M][N_or_K / P] of float pairs (mean, m2 = sum of
+ * squared deviations from that mean) over P consecutive columns, P = vg_gemm_ln_partial_cols().
+ * kind 0: consumer, C = f16(rstd (X@Wt^T - mean c1) + d_bias) with (mean, rstd) merged from the row's K / P partials of d_stats,
+ *         rstd = rsqrt((sum m2 + P sum (mean_i - mean)^2) / K + 1e-5); d_bias is c2.  d_C f16 with row stride ldc >= N (ldc % 8 == 0).
+ *         K % 128 == 0 (w4) or K % 256 == 0 (pp64), K <= 1024.
+ * kind 1: the same, then QuickGELU.
+ * kind 2: producer on the fp32 stream, ldc == N: d_resid f32 [M,N] += X@Wt^T + d_bias; d_x16 = f16 copy of the new d_resid; d_stats
+ *         written from it.
+ * kind 3: producer on the fp16 pair (k_gemm_f16_w4 only: VG_ERR_ARG with VG_GEMM_W4=0), ldc == N: t = (X@Wt^T + d_bias) + (hi + lo)
+ *         with hi = d_x16, lo = d_resid (both f16 [M,N], read and written): hi = f16(t), lo = f16(t - hi); d_stats of hi + lo. */
+int vg_gemm_ln(int kind, const void* d_X, const void* d_Wt, const float* d_bias, const float* d_c1, void* d_stats, void* d_C, int ldc,
+               void* d_resid, void* d_x16, int M, int N, int K, void* stream);
+/* P of vg_gemm_ln's partial statistics for the current VG_GEMM_W4: 128 (k_gemm_f16_w4) or 256 (k_gemm_f16_pp64) */
+int vg_gemm_ln_partial_cols(void);
+
 /* vg_gemm(dtype 1, epi 2) the way the tower launches its residual GEMMs (out_proj / c_proj, model.py:190-191): with scratch for a
  * split-K tail.  A 256 x 256 tile owns a CU, so a launch runs in rounds of n_cu tiles; the row tiles that do not fill complete rounds
  * (when they are at most half a round) are computed by several workgroups per tile, each over a slice of K, their fp32 partial tiles

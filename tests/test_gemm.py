@@ -186,6 +186,21 @@ def test_gemm_w4_equals_pp64_bit_for_bit(cuda, epi, shape, monkeypatch):
     if M <= 768:
         want = _ref(X.cpu(), W.cpu(), bias.cpu(), resid.cpu(), epi)
         assert (outs[0].float().cpu() - want.float()).abs().max().item() < 3e-3 * max(1.0, want.abs().max().item())
+    else:
+        # the large launches (every persistent w4 workgroup runs second and later tiles from prefetched pieces) against float64 too, on
+        # sampled rows: the first and last row of each 64-row group of every row tile (so every workgroup's first and last tile) + random rows
+        from gemm_ln_ref import quick_gelu
+        rows = (torch.arange(0, M, 256)[:, None] + torch.tensor([0, 63, 64, 127, 128, 191, 192, 255])[None, :]).flatten()
+        rows = torch.unique(torch.cat([rows, torch.randint(0, M, (256,), generator=g)])).to(cuda)
+        acc = X[rows].double() @ W.double().t()
+        want = acc if epi == 3 else acc + bias.double()
+        if epi == 1:
+            want = quick_gelu(want)
+        if epi == 2:
+            want = resid[rows].double() + want
+        err = (outs[0][rows].double() - want).abs().max().item()
+        print(f'w4 == pp64 {shape} epi {epi}: {len(rows)} sampled rows within {err:.2e} of float64')
+        assert err < 3e-3 * max(1.0, want.abs().max().item())
 
 
 @pytest.mark.gpu

@@ -507,6 +507,33 @@ def test_hip_tower_pair_residual_stream_agrees(cuda, monkeypatch):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize('tower,n', [('VIT_B16', 2), ('VIT_B16', 3), ('VIT_B32', 10), ('VIT_B32', 11)])
+def test_hip_pair_stream_switches_on_at_its_crop_count(cuda, tower, n, monkeypatch):
+    """The pair stream (`hl`) and the class-row last block (`cls_only`) both need the compact class-row buffers to fit in the qkv buffer
+    (vg_vit_encode's `cls_fits`): from 3 crops for ViT-B/16, from 11 for ViT-B/32.  Below that count both are off, so VG_VIT_RESID_HL=1
+    and =0 give bit-identical features; from it on the pair stream runs: the features differ, agree within 5e-4 and keep their distance
+    to the fp32 tower (as in test_hip_tower_pair_residual_stream_agrees)."""
+    from vilgod_amd.clip_wrapper import VitEncoder
+    wd = cw.synthetic_vit_weights(5, **dict(getattr(cw, tower), layers=2))
+    x = torch.randn(n, 3, 224, 224, generator=torch.Generator().manual_seed(n)).to(cuda)
+    feats = {}
+    for hl in ('1', '0'):
+        monkeypatch.setenv('VG_VIT_RESID_HL', hl)
+        feats[hl] = VitEncoder(wd, dtype='f16', device=cuda).encode(x).cpu()
+    assert torch.isfinite(feats['1']).all()
+    above = n >= {'VIT_B16': 3, 'VIT_B32': 11}[tower]
+    if not above:
+        assert torch.equal(feats['1'], feats['0'])
+        return
+    assert not torch.equal(feats['1'], feats['0'])       # (the pair stream ran)
+    f32 = VitEncoder(wd, dtype='f32', device=cuda).encode(x).cpu()
+    rel = ((feats['1'] - feats['0']).norm() / feats['0'].norm()).item()
+    d_x, d_hl = ((feats['0'] - f32).norm() / f32.norm()).item(), ((feats['1'] - f32).norm() / f32.norm()).item()
+    print(f'{tower} n = {n}: pair vs fp32 stream {rel:.2e}; to the fp32 tower {d_hl:.2e} (fp32 stream: {d_x:.2e})')
+    assert rel < 5e-4 and d_hl < 1.15 * d_x + 1e-5
+
+
+@pytest.mark.gpu
 def test_hip_tower_is_deterministic_with_two_encodes_in_flight(cuda):
     """Race screen for k_gemm_f16_w4 under the pipeline's conditions: two encodes in flight on two streams (persistent workgroups of one
     launch start on CUs as the other launch's workgroups leave them; DMA pieces of a tile are waited for with counts that assume in-order

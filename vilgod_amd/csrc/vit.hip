@@ -2124,7 +2124,7 @@ static int launch_gemm_pp64(const void* X, const void* Wt, const float* bias, vo
                             hipStream_t st, long long* trace = nullptr, const float* ln_c1 = nullptr, LnPartial* ln_stats = nullptr,
                             f16* ln_x16 = nullptr) {
     if (M % 256 || N % 256 || K % 64 || K / 64 < 2) return VG_ERR_ARG;
-    if (LN == 1 && (K % 256 || !ln_c1 || !ln_stats)) return VG_ERR_ARG;
+    if (LN == 1 && (K % 256 || K > 1024 || !ln_c1 || !ln_stats)) return VG_ERR_ARG;      // the consumer merges at most 4 partials (pt[4])
     if (LN == 2 && (ldc != N || !ln_stats || !ln_x16)) return VG_ERR_ARG;
     auto kern = k_gemm_f16_pp64<EPI, TRACE, PERSIST, LN>;
     const int lds = 5 * 32768;
@@ -2692,10 +2692,14 @@ int vg_vit_encode(vg_vit* v, const void* d_crops, int input_kind, int n_crops, v
     const bool rh = v->resid_h;
     bool ln1_done = false;
     f16* xh = (f16*)x;                // the residual stream lives in the same workspace region, as fp16 when `rh`
+    // The last block runs on the compact class-token rows (`cls_only` below) only if their buffers fit in the qkv buffer (statistics sized
+    // like vg_vit_workspace_bytes: W / 64 partials per row, k_gemm_f16_x2's count).  With ViT-B/16 that holds from 3 crops, ViT-B/32 from
+    // 11, ViT-L/14 from 2 (tests/test_vit.py pins the boundary).
+    const int64_t Mc = pad128(n_crops);
+    const bool cls_fits = Mc * W * 16 + Mc * (W / 64) * 8 <= Mp * (3 * W + 256) * es;
     // the stream as an fp16 pair (VG_VIT_RESID_HL): hi = x16 (what in_proj / c_fc read anyway), lo in the fp32 stream's region; every full-row
-    // residual GEMM is then a folded-LayerNorm producer (the last block runs on the compact fp32 class rows: the same condition as `cls_only`)
-    const bool hl = v->resid_hl && fold && !rh && v->dtype == 1 && L > 1 && W % 256 == 0 &&
-                    pad128(n_crops) * W * 16 + pad128(n_crops) * (W / 64) * 8 <= Mp * (3 * W + 256) * es;
+    // residual GEMM is then a folded-LayerNorm producer (the last block runs on the compact fp32 class rows: hence `cls_fits`)
+    const bool hl = v->resid_hl && fold && !rh && v->dtype == 1 && L > 1 && W % 256 == 0 && cls_fits;
     f16* xlo = (f16*)x;
     if (rh)
         hipLaunchKernelGGL((k_embed_lnpre<f16>), dim3((unsigned)((Mp + 3) / 4)), dim3(256), 0, st, pe, (const float*)need("class_embedding"),
@@ -2749,10 +2753,8 @@ int vg_vit_encode(vg_vit* v, const void* d_crops, int input_kind, int n_crops, v
         // So the block computes all keys and values, the class token's attention row, and then runs its three remaining GEMMs on
         // the n_crops class-token rows alone (compacted, padded to the row tile) instead of on n_crops x T rows: the same value
         // per element -- a row's dot products do not depend on which rows share its tile -- for 1 / T of the work.
-        const int64_t Mc_ = pad128(n_crops);
-        const bool cls_fits = Mc_ * W * 16 + Mc_ * (W / 64) * 8 <= Mp * (3 * W + 256) * es;       // the compact buffers live in the qkv buffer
-                                                                                                   // (statistics sized like vg_vit_workspace_bytes: W / 64 partials per row, k_gemm_f16_x2's count)
-        const bool cls_only = v->cls_last && fold && !rh && l == L - 1 && L > 1 && cls_fits;
+        const bool cls_only = v->cls_last && fold && !rh && l == L - 1 && L > 1 && cls_fits;     // (the compact buffers live in the qkv buffer)
+        if (hl && l == L - 1 && !cls_only) return VG_ERR_ARG;          // the pair stream has no full-row last block (resid_hl implies cls_last)
         if (cls_only && W % 256 == 0) {
             // ... and of in_proj's three thirds that block needs K and V for every row but Q for the class-token rows only (round 5: a
             // third of the launch, 270 -> ~190 us per frame): in_proj's K / V rows (weight rows [W, 3W)) over all tokens, its Q rows over
@@ -2761,15 +2763,15 @@ int vg_vit_encode(vg_vit* v, const void* d_crops, int input_kind, int n_crops, v
             // that nobody reads (a query row never meets another query row).  Same kernel, same K loop per row: the same bits.
             const int nst = v->gemm_w4 ? W >> 7 : W >> 8;        // partial statistics per row: per 128 columns (k_gemm_f16_w4) or per 256
             char* cb = (char*)mlp;
-            f16* x16q = (f16*)cb;              cb += Mc_ * W * 2;
-            f16* qc = (f16*)cb;                cb += Mc_ * W * 2;
+            f16* x16q = (f16*)cb;              cb += Mc * W * 2;
+            f16* qc = (f16*)cb;                cb += Mc * W * 2;
             LnPartial* lnq = (LnPartial*)cb;
             rc = launch_gemm<EPI_BIAS, 1>(v, x16, (const f16*)fw1 + (size_t)W * W, f1c2 + W, (f16*)qkv + W, nullptr, (int)Mp, 2 * W, W, st, qkv_ld,
                                           f1c1 + W, lnst);
             if (rc) return rc;
-            hipLaunchKernelGGL(k_gather_cls_ln, dim3((unsigned)Mc_), dim3(256), 0, st, (const f16*)x16, (const LnPartial*)lnst, x16q, lnq, n_crops, T, W, nst);
+            hipLaunchKernelGGL(k_gather_cls_ln, dim3((unsigned)Mc), dim3(256), 0, st, (const f16*)x16, (const LnPartial*)lnst, x16q, lnq, n_crops, T, W, nst);
             VG_LAUNCH_CHECK();
-            rc = launch_gemm<EPI_BIAS, 1>(v, x16q, fw1, f1c2, qc, nullptr, (int)Mc_, W, W, st, 0, f1c1, lnq);
+            rc = launch_gemm<EPI_BIAS, 1>(v, x16q, fw1, f1c2, qc, nullptr, (int)Mc, W, W, st, 0, f1c1, lnq);
             if (rc) return rc;
             hipLaunchKernelGGL(k_scatter_cls_q, dim3((unsigned)n_crops), dim3(256), 0, st, (const f16*)qc, (f16*)qkv, T, W, qkv_ld);
             VG_LAUNCH_CHECK();
@@ -2805,7 +2807,6 @@ int vg_vit_encode(vg_vit* v, const void* d_crops, int input_kind, int n_crops, v
         if (cls_only) {
             // compact buffers inside the qkv buffer (dead once the attention has run): residual rows, attention rows, fp16 copy, hidden
             // activations, row statistics
-            const int64_t Mc = pad128(n_crops);
             char* cb = (char*)qkv;
             float* xc = (float*)cb;            cb += Mc * W * 4;
             f16* hc = (f16*)cb;                cb += Mc * W * 2;
@@ -2891,6 +2892,38 @@ int vg_gemm(int dtype, int epi, const void* d_X, const void* d_Wt, const float* 
         case 4: return dtype == 1 ? launch_gemm<EPI_BIAS_RESID_H>(&v, d_X, d_Wt, d_bias, d_C, d_resid, M, N, K, st) : VG_ERR_ARG;
     }
     return VG_ERR_ARG;
+}
+
+/* The folded-LayerNorm epilogues of the projection GEMM, alone (test entry point; header: vilgod_hip.h).  Reuses the tower's own
+ * instantiations: kind 0 / 1 = the consumer (in_proj / c_fc), 2 = the producer on the fp32 stream, 3 = the producer on the fp16 pair. */
+int vg_gemm_ln(int kind, const void* d_X, const void* d_Wt, const float* d_bias, const float* d_c1, void* d_stats, void* d_C, int ldc,
+               void* d_resid, void* d_x16, int M, int N, int K, void* stream) {
+    if (!d_X || !d_Wt || !d_bias || !d_stats || ldc < N || ldc % 8) return VG_ERR_ARG;
+    vg_vit v;
+    v.dtype = 1;
+    if (v.gemm_w4 && K < 256) return VG_ERR_ARG;       // (launch_gemm would take k_gemm_f16_pp64 there: 256-column partials)
+    hipStream_t st = (hipStream_t)stream;
+    LnPartial* stats = (LnPartial*)d_stats;
+    switch (kind) {
+        case 0:
+        case 1:
+            if (!d_c1 || !d_C) return VG_ERR_ARG;
+            return kind == 0 ? launch_gemm<EPI_BIAS, 1>(&v, d_X, d_Wt, d_bias, d_C, nullptr, M, N, K, st, ldc, d_c1, stats)
+                             : launch_gemm<EPI_BIAS_GELU, 1>(&v, d_X, d_Wt, d_bias, d_C, nullptr, M, N, K, st, ldc, d_c1, stats);
+        case 2:
+            if (!d_resid || !d_x16) return VG_ERR_ARG;
+            return launch_gemm<EPI_BIAS_RESID, 2>(&v, d_X, d_Wt, d_bias, nullptr, (float*)d_resid, M, N, K, st, ldc, nullptr, stats, (f16*)d_x16);
+        case 3:
+            if (!d_resid || !d_x16) return VG_ERR_ARG;
+            return launch_gemm<EPI_BIAS_RESID_HL, 2>(&v, d_X, d_Wt, d_bias, nullptr, (float*)d_resid, M, N, K, st, ldc, nullptr, stats, (f16*)d_x16);
+    }
+    return VG_ERR_ARG;
+}
+
+/* columns per (mean, m2) partial of the family vg_gemm_ln uses now (VG_GEMM_W4, read per call) */
+int vg_gemm_ln_partial_cols(void) {
+    vg_vit v;
+    return v.gemm_w4 ? 128 : 256;
 }
 
 /* vg_gemm epi 2 (dtype 1) with scratch for the split-K tail (launch_gemm / splitk_plan): what the tower's residual GEMMs run.  Row tiles
