@@ -339,6 +339,23 @@ int vg_cluster_filter(const float* d_points, int stride, const int32_t* d_index,
 int vg_cluster_boxes(const float* d_points, int stride, const int32_t* d_index, const int32_t* d_seg_off, int n_clusters,
                      double* d_box7, float* d_aux3, void* stream);
 
+/* fit_bounding_boxes_simple, static branch (src/vilgod/zero_shot_detector.py:451, :477, :672) with method closeness_rectangle
+ * (criterion 0, src/utils/pointcloud_utils.py:170-229) or variance_rectangle (criterion 1, :231-288): the L-shape search over
+ * the angles of d_angle_table, the first angle of the largest criterion, the rectangle there and the box of zero_shot_detector.py:452-461.
+ * d_angle_table: [n_angles][VG_LSHAPE_TABLE_STRIDE] float64 rows {cos a, sin a, cos(a + pi/2), sin(a + pi/2), a, a + pi/2,
+ * a + pi/2 + pi/2, (a + pi/2) + pi/2} with a = np.arange(0, 90 + delta, delta)[k] / 180 * np.pi; cos / sin rounded to float32 for
+ * closeness (the reference's components dtype).  delta_zero: closeness only (> 0).  d_work: [n_clusters, n_angles] float64, the
+ * criterion of every (cluster, angle).  d_box7[c] = {cx,cy,cz,l,w,h+0.3,rz}; d_aux[c] = {chosen angle index, its criterion, rz
+ * before the l/w swap}.  VG_ERR_ARG before any device work for a bad criterion, n_angles outside [1, VG_LSHAPE_MAX_ANGLES]
+ * (delta >= 0.01 degrees), delta_zero <= 0 with closeness, or null pointers with n_clusters > 0; n_clusters == 0 is a no-op. */
+#define VG_LSHAPE_CLOSENESS 0
+#define VG_LSHAPE_VARIANCE 1
+#define VG_LSHAPE_TABLE_STRIDE 8
+#define VG_LSHAPE_MAX_ANGLES 9001
+int vg_cluster_lshape(const float* d_points, int stride, const int32_t* d_index, const int32_t* d_seg_off, int n_clusters,
+                      int criterion, const double* d_angle_table, int n_angles, double delta_zero, double* d_work,
+                      double* d_box7, double* d_aux, void* stream);
+
 /* Detection.cluster_mass_center (src/dataclass/objects.py:121-123: np.median(cluster_points, axis=0)) of every packed cluster over the
  * first n_cols columns of the point rows (the tracker reads all five: src/vilgod/tracker.py:52-59, objects.py:238-306).  Exact
  * order statistics; an even count gives the float32 mean of the two middle values like np.median.  d_median: [n_clusters, n_cols] f32. */

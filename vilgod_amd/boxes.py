@@ -70,6 +70,59 @@ def box_from_rectangle(corners, rz, zmin, zmax):
     return np.array([c[0], c[1], zmin + height / 2, l, w, height + 0.3, rz])
 
 
+# ---- the method of fit_bounding_boxes_simple -----------------------------------------------------------------------------------
+# `method: {name, args}` names a function of the reference's pointcloud_utils (zero_shot_detector.py:451, :477, :672).  The L-shape
+# fits run on the GPU in both box modes (csrc/lshape.hip, PseudoLabelPipeline.lshape_boxes); `box_mode` only concerns
+# minimum_bounding_rectangle.  PCA_rectangle is not offered: its axes and signs depend on scikit-learn's solver.
+LSHAPE_METHODS = {                                        # name -> (vg_cluster_lshape criterion, the reference's keyword defaults)
+    'closeness_rectangle': (0, {'delta': 2, 'delta_zero': 1e-2}),          # pointcloud_utils.py:199
+    'variance_rectangle': (1, {'delta': 0.1}),                               # :231
+}
+BOX_METHODS = ('minimum_bounding_rectangle',) + tuple(LSHAPE_METHODS)
+LSHAPE_MAX_ANGLES = 9001                                  # include/vilgod_hip.h VG_LSHAPE_MAX_ANGLES (delta >= 0.01 degrees)
+
+
+def box_method(method):
+    """fit_bounding_boxes_simple's `method` ({'name', 'args'} dict, config node or None = minimum_bounding_rectangle)
+    -> (name, keyword arguments with the reference's defaults).  An unknown name raises NotImplementedError, an unknown keyword
+    TypeError (as the reference's call `getattr(pointcloud_utils, name)(points, **args)` would)."""
+    if method is None:
+        return 'minimum_bounding_rectangle', {}
+    if isinstance(method, dict):
+        name, args = method['name'], method.get('args')
+    else:
+        name, args = method.name, getattr(method, 'args', None)
+    args = dict(args or {})
+    if name not in BOX_METHODS:
+        raise NotImplementedError(f'{name}: fit_bounding_boxes_simple supports the methods {", ".join(BOX_METHODS)}')
+    defaults = LSHAPE_METHODS[name][1] if name in LSHAPE_METHODS else {}
+    for k in args:
+        if k not in defaults:
+            raise TypeError(f'{name}() got an unexpected keyword argument {k!r}')
+    return name, dict(defaults, **args)
+
+
+def lshape_angle_table(name, args):
+    """The angles the reference's L-shape search visits and the components it builds for them -> [A, 8] float64 rows
+    {cos a, sin a, cos(a + pi/2), sin(a + pi/2), a, a + pi/2, a + pi/2 + pi/2, (a + pi/2) + pi/2} (layout: vg_cluster_lshape).
+    a = np.arange(0, 90 + delta, delta) / 180 * np.pi (pointcloud_utils.py:174-175, :234-235); cos / sin are evaluated per scalar
+    as there and rounded to float32 for closeness_rectangle (its components are float32, :176-179); the flipped orientation's are
+    evaluated from the float64 sum a + pi/2 (:208-212, :269-273), not swapped from a's; the last two columns are the rz of the
+    l / w swap (zero_shot_detector.py:455-457)."""
+    delta = args['delta']
+    if not delta > 0:
+        raise ValueError(f'{name}: delta must be > 0 (got {delta})')
+    ang = np.arange(0, 90 + delta, delta) / 180. * np.pi
+    if not 1 <= len(ang) <= LSHAPE_MAX_ANGLES:
+        raise ValueError(f'{name}: delta={delta} gives {len(ang)} angles; at most {LSHAPE_MAX_ANGLES} (delta >= 0.01 degrees)')
+    dt = np.float32 if name == 'closeness_rectangle' else np.float64
+    t = np.empty((len(ang), 8))
+    for k, a in enumerate(ang):
+        f = a + np.pi / 2
+        t[k] = (dt(np.cos(a)), dt(np.sin(a)), dt(np.cos(f)), dt(np.sin(f)), a, f, a + np.pi / 2, f + np.pi / 2)
+    return t
+
+
 def reference_boxes_packed(xy_packed, seg, zmin, zmax):
     """Boxes of clusters whose xy points are already packed cluster after cluster ([P,2] float32, seg offsets)."""
     C = len(seg) - 1

@@ -32,6 +32,7 @@ SOURCES = {
     'hdbscan_tree.cpp': ['-ffp-contract=off'],
     'hdbscan_device.hip': ['-ffp-contract=off'],
     'segment.hip': ['-ffp-contract=off'],
+    'lshape.hip': ['-ffp-contract=off'],
     'vit.hip': [],
 }
 

@@ -123,6 +123,7 @@ class PseudoLabelPipeline:
             from . import boxes as _boxes
             _boxes._pool(self.box_workers)       # the helper processes import numpy / scipy (~1 s) while the tower's weights are set up
         self._xy_pinned = None
+        self._lshape_tables = {}                 # L-shape angle tables on the device, per (method, args); shared by the worker clones
         self._ransac_work = torch.zeros(100 * 36 + 64, dtype=torch.uint8, device=self.device)
         self.timings = {}
         # CU-masked streams for the frames in flight (vilgod_amd/streams.py): the worker streams that carry a frame's front stage
@@ -537,6 +538,29 @@ class PseudoLabelPipeline:
               'vg_cluster_boxes')
         return box, aux
 
+    def lshape_boxes(self, d_X, d_index, d_seg, name, args=None):
+        """closeness_rectangle / variance_rectangle (pointcloud_utils.py:170-288) and the box of zero_shot_detector.py:452-461 for the
+        packed clusters, on the GPU in either box mode (csrc/lshape.hip).  args: the method's keywords (the reference's defaults fill
+        the rest).  -> (CUDA [C,7] float64 boxes, CUDA [C,3] float64 aux: chosen angle index, its criterion, rz before the l/w swap)."""
+        from .boxes import LSHAPE_METHODS, box_method, lshape_angle_table
+        name, args = box_method({'name': name, 'args': args})
+        if name not in LSHAPE_METHODS:
+            raise ValueError(f'{name} is not an L-shape fit ({", ".join(LSHAPE_METHODS)})')
+        key = (name, tuple(sorted(args.items())))
+        tab = self._lshape_tables.get(key)
+        if tab is None:
+            tab = torch.from_numpy(lshape_angle_table(name, args)).to(self.device)
+            torch.cuda.current_stream(self.device).synchronize()           # (other workers' streams read it from now on)
+            self._lshape_tables[key] = tab
+        C = d_seg.numel() - 1
+        A = tab.shape[0]
+        work = torch.empty((max(C, 1), A), dtype=torch.float64, device=self.device)
+        box = torch.empty((C, 7), dtype=torch.float64, device=self.device)
+        aux = torch.empty((C, 3), dtype=torch.float64, device=self.device)
+        check(lib.vg_cluster_lshape(ptr(d_X), d_X.stride(0), ptr(d_index), ptr(d_seg), C, LSHAPE_METHODS[name][0], ptr(tab), A,
+                                    float(args.get('delta_zero', 1.0)), ptr(work), ptr(box), ptr(aux), stream_ptr()), 'vg_cluster_lshape')
+        return box, aux
+
     def cluster_medians(self, d_X, d_index, d_seg):
         """Detection.cluster_mass_center (objects.py:121-123) of the packed clusters over ALL columns of d_X -> CUDA [C, cols] f32."""
         C = d_seg.numel() - 1
@@ -568,15 +592,21 @@ class PseudoLabelPipeline:
         st = stats.cpu().numpy()
         return st[:, 1], st[:, 2]
 
-    def fit_boxes(self, d_X, index, seg, d_index=None, d_seg=None, xy_host=None, zmin=None, zmax=None):
+    def fit_boxes(self, d_X, index, seg, d_index=None, d_seg=None, xy_host=None, zmin=None, zmax=None, method=None):
         """fit_bounding_boxes_simple, static branch (zero_shot_detector.py:444-462), for the packed clusters (index, seg).
-        -> [C,7] float64 numpy boxes in the reference frame, by `self.box_mode` (vilgod_amd/boxes.py)."""
+        method: the stage's {name, args} (None = minimum_bounding_rectangle, by `self.box_mode`, vilgod_amd/boxes.py);
+        closeness_rectangle / variance_rectangle run `lshape_boxes` in either box mode.
+        -> [C,7] float64 numpy boxes in the reference frame."""
+        from .boxes import box_method
+        name, args = box_method(method)
         C = len(seg) - 1
         if C == 0:
             return np.zeros((0, 7))
         if d_index is None:
             d_index = torch.from_numpy(np.ascontiguousarray(index, dtype=np.int32)).to(self.device)
             d_seg = torch.from_numpy(np.ascontiguousarray(seg, dtype=np.int32)).to(self.device)
+        if name != 'minimum_bounding_rectangle':
+            return self.lshape_boxes(d_X, d_index, d_seg, name, args)[0].cpu().numpy()
         if self.box_mode == 'fast':
             return self.boxes(d_X, d_index, d_seg)[0].cpu().numpy()
         return self.fit_boxes_async(d_X, index, seg, d_index, d_seg, xy_host, zmin, zmax).result()

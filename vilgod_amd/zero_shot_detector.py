@@ -34,6 +34,7 @@ import numpy as np
 import torch
 
 from . import dist as vdist
+from .boxes import box_method
 from .frame_state import FrameState, pack_clusters, vote
 from .pipeline import PseudoLabelPipeline
 
@@ -412,7 +413,8 @@ class ZeroShotDetector:
         if not back:
             return False
         if 'fit_bounding_boxes_simple' in back:
-            if self.tracker is None or len(self.tracker.tracks_valid) == 0 or self.pipe.box_mode != 'reference':
+            if self.tracker is None or len(self.tracker.tracks_valid) == 0 or self.pipe.box_mode != 'reference' \
+                    or self._configured_box_method()[0] != 'minimum_bounding_rectangle':
                 return False
             tracked = {}
             for t in self.tracker.tracks_valid:
@@ -706,8 +708,22 @@ class ZeroShotDetector:
                 'names': np.array(p.mapped_names, dtype=object), 'fine_names': np.array(p.class_list, dtype=object),
                 # the static rectangles of the same clusters (box_mode='reference': a helper process per request) are computed while
                 # the GPU encodes the crops; fit_bounding_boxes_simple collects them (they do not depend on the classes)
+                # -- min-area rectangles only: the request carries no method, and an L-shape fit runs on the GPU in the box stage
                 'prefetch_boxes': (p.box_mode == 'reference' and 'fit_bounding_boxes_simple' in active and 'classification' in active
-                                   and active.index('fit_bounding_boxes_simple') > active.index('classification'))}
+                                   and active.index('fit_bounding_boxes_simple') > active.index('classification')
+                                   and self._configured_box_method()[0] == 'minimum_bounding_rectangle')}
+
+    def _configured_box_method(self):
+        """(name, args) of the configured fit_bounding_boxes_simple stage's `method` (minimum_bounding_rectangle when absent; args
+        None for a method the stage will refuse -- it raises in its own turn)."""
+        for t in self.cfg.pipeline:
+            if t['name'] == 'fit_bounding_boxes_simple':
+                m = (t['args'] or {}).get('method')
+                try:
+                    return box_method(m)
+                except (NotImplementedError, TypeError):
+                    return (m['name'] if isinstance(m, dict) else m.name), None
+        return box_method(None)
 
     def _classify_frame(self, pw, fnr, ctx):
         """classification for one frame on pipeline handle `pw`."""
@@ -742,9 +758,9 @@ class ZeroShotDetector:
         self.sync_lidar_frames()
 
     def fit_bounding_boxes_simple(self, method, **kwargs):
-        mname = method['name'] if isinstance(method, dict) else method.name
-        if mname != 'minimum_bounding_rectangle':
-            raise NotImplementedError(f'{mname}: only minimum_bounding_rectangle (the configured method) has a kernel')
+        # method: minimum_bounding_rectangle (box_mode decides where it runs), closeness_rectangle or variance_rectangle (GPU, any
+        # box_mode) with the reference's keywords; other names raise NotImplementedError, unknown keywords TypeError
+        method = box_method(method)
         valid_only, fg_only = kwargs.get('valid_only', False), kwargs.get('fg_only', False)
         ckey = kwargs.get('classification_key', None)
         if self.tracker is not None and len(self.tracker.tracks_valid) > 0:
@@ -754,7 +770,7 @@ class ZeroShotDetector:
                 return                                   # boxes exist and force is off: upstream skips the stage (:424-432)
             for fs in self.lidar_frame_list:
                 fs.boxes = None
-            self._fit_boxes_tracked(valid_only)
+            self._fit_boxes_tracked(valid_only, method)
             self._box_prefetch.clear()
             self._host_X.clear()                         # host copies of the frames' points: only this stage and the prefetch read them
             self.sync_lidar_frames()
@@ -773,17 +789,18 @@ class ZeroShotDetector:
             if len(rows) == 0:
                 continue
             _, X = self._ref_and_nonground(fnr)
-            jobs.append((fs, rows, self._boxes_of_rows(fnr, rows, X)))
+            jobs.append((fs, rows, self._boxes_of_rows(fnr, rows, X, method)))
         for fs, rows, fut in jobs:
             fs.boxes[rows] = fut.result()
         self._box_prefetch.clear()
         self._host_X.clear()
         self.sync_lidar_frames()
 
-    def _boxes_of_rows(self, fnr, rows, X):
+    def _boxes_of_rows(self, fnr, rows, X, method=None):
         """-> object with .result() -> [len(rows),7]: from the request `classification` already sent for this frame when it covers
-        the rows, else a new request."""
-        pre = self._box_prefetch.get(fnr)
+        the rows (min-area rectangles: the only method it requests), else a new request.  method: (name, args) of box_method."""
+        method = method or box_method(None)
+        pre = self._box_prefetch.get(fnr) if method[0] == 'minimum_bounding_rectangle' else None
         if pre is not None:
             pos = {r: i for i, r in enumerate(pre[0])}
             if all(int(r) in pos for r in rows):
@@ -793,16 +810,20 @@ class ZeroShotDetector:
                     def result(self_inner):
                         return np.asarray(fut.result())[sel]
                 return _Sel()
-        return self._fit_rows(fnr, rows, X, wait=False)
+        return self._fit_rows(fnr, rows, X, wait=False, method=method)
 
-    def _fit_rows(self, fnr, rows, X, wait=True):
-        """Static-branch boxes of clusters `rows` of frame fnr (pipeline.fit_boxes: reference or fast mode); wait=False returns an
-        object with .result() (reference mode: the host part runs in a helper process meanwhile)."""
+    def _fit_rows(self, fnr, rows, X, wait=True, method=None):
+        """Static-branch boxes of clusters `rows` of frame fnr (pipeline.fit_boxes: min-area rectangles in reference or fast mode, the
+        L-shape fits on the GPU); wait=False returns an object with .result() (reference mode: the host part runs in a helper process
+        meanwhile).  method: (name, args) of box_method, None = minimum_bounding_rectangle."""
         from .boxes import _Done
         fs = self.lidar_frame_list[fnr]
         parts = [fs.cluster_index(c) for c in rows]
         index = np.concatenate(parts).astype(np.int32)
         seg = np.r_[0, np.cumsum([len(p) for p in parts])].astype(np.int32)
+        if method is not None and method[0] != 'minimum_bounding_rectangle':
+            boxes = self.pipe.fit_boxes(X, index, seg, method={'name': method[0], 'args': method[1]})
+            return boxes if wait else _Done(boxes)
         if self.pipe.box_mode != 'reference':
             return self.pipe.fit_boxes(X, index, seg) if wait else _Done(self.pipe.fit_boxes(X, index, seg))
         fut = self.pipe.fit_boxes_async(X, index, seg, xy_host=self._points_host(fnr))
@@ -909,7 +930,7 @@ class ZeroShotDetector:
             x3 = self._host_X3[fnr] = np.ascontiguousarray(self._points_host(fnr)[:, :3])
         return x3.take(self.lidar_frame_list[fnr].cluster_index(row), axis=0)
 
-    def _fit_boxes_tracked(self, valid_only):
+    def _fit_boxes_tracked(self, valid_only, method=None):
         """The track branch of fit_bounding_boxes_simple (zero_shot_detector.py:463-684): the per-detection rectangle boxes come
         from the GPU kernel (one launch per frame over all tracked clusters), the motion logic is host code."""
         from .tracking import DetectionTable, fit_track_boxes
@@ -923,7 +944,7 @@ class ZeroShotDetector:
             for fnr, rows in tracked.items():                # every frame's request goes out before the first answer is awaited
                 rows = sorted(rows)
                 _, X = self._ref_and_nonground(fnr)
-                jobs.append((fnr, rows, self._boxes_of_rows(fnr, rows, X)))
+                jobs.append((fnr, rows, self._boxes_of_rows(fnr, rows, X, method)))
         with self._part('boxes.await_static'):
             for fnr, rows, fut in jobs:
                 for r, b in zip(rows, fut.result()):
