@@ -156,6 +156,17 @@ int vg_gemm_resid_splitk(const void* d_X, const void* d_Wt, const float* d_bias,
  * Exposed so that the kernels can be unit-tested against a plain fp32 attention. */
 int vg_attention(const void* d_qkv, void* d_out, int n_crops, int T, int W, int heads, int ld, void* stream);
 
+/* Every attention path of the tower alone (model.py:175-187 via nn.MultiheadAttention), for unit tests against a float64
+ * softmax(q k^T / 8) v; vg_attention's layout of d_qkv / d_out.  Handle-less: VG_ATT_TR / VG_ATT_STAGGER are read per call.
+ * dtype 1: the fp16 kernels as vg_vit_encode launches them, with the caller's q_tiles: only the first q_tiles 32-row query tiles of
+ *   every crop are computed and written (1 <= q_tiles <= ceil(T / 32); the tower passes 1 in its last block, whose class-token row
+ *   alone is used, model.py:235), the other rows of d_out are left as they were.  ld >= 3 W, ld % 8 == 0.
+ * dtype 0: k_attention_f32 (the fp32 parity mode) on float32 d_qkv / d_out.  That kernel hard-codes ld = 3 W and computes every row:
+ *   ld != 3 W or q_tiles != ceil(T / 32) is VG_ERR_ARG, and so is a T whose K, V and probability rows exceed its 160 KiB of LDS
+ *   (T * 145 * 4 bytes: T <= 282, the limit of vg_vit_create).
+ * Anything else (T outside 1 .. 1024, heads * 64 != W, null pointers) is VG_ERR_ARG and nothing is launched. */
+int vg_attention_rows(int dtype, const void* d_qkv, void* d_out, int n_crops, int T, int W, int heads, int ld, int q_tiles, void* stream);
+
 /* ---- captured classification: the hipGraph loop of BASELINE config 5 ------------------------------------------------
  * vg_vit_encode + vg_clip_scores of one frame (the reference's per-chunk model.encode_image + softmax, clip_utils.py:37-61) as ONE
  * hipGraph per distinct crop count: captured on the first frame that has that many crops, replayed for every later one

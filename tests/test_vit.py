@@ -155,8 +155,11 @@ def test_hip_clip_scores_exact_small(cuda):
 @pytest.mark.gpu
 @pytest.mark.parametrize('n_crops,T', [(3, 197), (1, 50), (2, 224), (5, 33)])
 def test_hip_attention_alone(cuda, n_crops, T):
-    """k_attention_f16 through vg_attention against a plain torch fp32 attention of the same fp16 inputs:
-    softmax(q k^T / 8) v per (crop, head), model.py:175-187.  fp16 probabilities / outputs -> |err| <= 2e-3 * max|v|."""
+    """k_attention_f16 through vg_attention against the float64 attention of the same fp16 inputs, softmax(q k^T / 8) v per (crop, head),
+    model.py:175-187, under the derived per-element bound of tests/attention_ref.py (fp16 probabilities / outputs; several times tighter
+    than the flat 2e-3 * max|v| this test used before), out pre-filled with NaN between guard rows."""
+    import ctypes
+    import attention_ref as R
     from vilgod_amd._lib import lib, ptr, stream_ptr, check
     W, H = 768, 12
     ld = 3 * W + 64
@@ -164,12 +167,12 @@ def test_hip_attention_alone(cuda, n_crops, T):
     qkv = torch.zeros(n_crops * T, ld, dtype=torch.float16)
     qkv[:, :3 * W] = (torch.randn(n_crops * T, 3 * W, generator=g) * torch.tensor([1.5] * W + [1.0] * W + [2.0] * W)).half()
     d_qkv = qkv.to(cuda)
-    out = torch.zeros(n_crops * T, W, dtype=torch.float16, device=cuda)
-    check(lib.vg_attention(ptr(d_qkv), ptr(out), n_crops, T, W, H, ld, stream_ptr()))
-    q, k, v = [qkv[:, i * W:(i + 1) * W].float().reshape(n_crops, T, H, 64).transpose(1, 2) for i in range(3)]
-    want = (torch.softmax(q @ k.transpose(-1, -2) * 0.125, dim=-1) @ v).transpose(1, 2).reshape(n_crops * T, W)
-    err = (out.float().cpu() - want).abs().max().item()
-    assert err < 2e-3 * v.abs().max().item(), err
+    buf = R.guarded_out(n_crops * T, W, torch.float16, cuda)
+    check(lib.vg_attention(ptr(d_qkv), ctypes.c_void_p(buf.data_ptr() + W * 2), n_crops, T, W, H, ld, stream_ptr()))
+    torch.cuda.synchronize()
+    want, A = R.reference(qkv, n_crops, T, W, H)
+    worst = R.check(buf, want, R.bound_f16(qkv, n_crops, T, W, H, want, A), n_crops, T)
+    print(f'T={T}: worst |got - want| / bound = {worst:.3f}')
 
 
 @pytest.mark.gpu

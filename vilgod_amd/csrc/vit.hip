@@ -2871,6 +2871,30 @@ int vg_attention(const void* d_qkv, void* d_out, int n_crops, int T, int W, int 
                                    !(tr_env && atoi(tr_env) == 0), !(sg_env && atoi(sg_env) == 0));
 }
 
+/* Every attention path of the tower, alone (test entry point; header: vilgod_hip.h).  dtype 1: launch_attention with the caller's q_tiles
+ * (the class-row-only launch of the last block passes 1); dtype 0: k_attention_f32 as vg_vit_encode launches it. */
+int vg_attention_rows(int dtype, const void* d_qkv, void* d_out, int n_crops, int T, int W, int heads, int ld, int q_tiles, void* stream) {
+    if (!d_qkv || !d_out || n_crops <= 0 || T < 1 || T > AL_MAXT || heads <= 0 || heads * 64 != W || ld < 3 * W) return VG_ERR_ARG;
+    if (q_tiles < 1 || q_tiles > (T + 31) / 32) return VG_ERR_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == 1) {
+        if (ld % 8) return VG_ERR_ARG;                  // (16-byte loads of the rows)
+        const char* tr_env = getenv("VG_ATT_TR");       // read per call, on the caller's thread, as vg_attention does
+        const char* sg_env = getenv("VG_ATT_STAGGER");
+        return launch_attention<false>((const f16*)d_qkv, (f16*)d_out, T, W, heads, ld, n_crops * heads, nullptr, st, q_tiles,
+                                       !(tr_env && atoi(tr_env) == 0), !(sg_env && atoi(sg_env) == 0));
+    }
+    if (dtype != 0) return VG_ERR_ARG;
+    // k_attention_f32 hard-codes ld = 3 W and computes every row; its K, V and probability rows must fit the LDS it requests (vg_vit_create)
+    if (ld != 3 * W || q_tiles != (T + 31) / 32) return VG_ERR_ARG;
+    const size_t lds = ((size_t)T * 65 + (size_t)T * 64 + 16 * (size_t)T) * sizeof(float);
+    if (lds > 160 * 1024) return VG_ERR_ARG;
+    VG_CHECK(hipFuncSetAttribute((const void*)k_attention_f32, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    hipLaunchKernelGGL(k_attention_f32, dim3(n_crops * heads), dim3(256), lds, st, (const float*)d_qkv, (float*)d_out, T, W, heads);
+    VG_LAUNCH_CHECK();
+    return VG_OK;
+}
+
 #ifdef VG_DEV      // development aids (tools/dev/vilgod_hip_dev.h): ablations, cycle-stamp traces
 #include "dev/vit_dev_entry.inc"
 #endif  // VG_DEV
