@@ -343,6 +343,56 @@ int vg_cluster_filter(const float* d_points, int stride, const int32_t* d_index,
                       const double* d_plane4, int min_points, int max_points, double max_min_height, double min_max_height,
                       double min_height, double max_height, float* d_stats6, uint8_t* d_valid, void* stream);
 
+/* Detection.filter with ANY of the filters of src/utils/cluster_utils.py and the and / or / required combination of
+ * src/dataclass/objects.py:158-181 (cluster_utils.py:66-89 validate_cluster is the same formula):
+ *   valid = (all(and) or any(or)) and all(and + required),   all([]) = True, any([]) = False.
+ * Filters, in the order of d_verdict's columns:
+ *   number_points  cluster_utils.py:14-15      height          :48-49 (float32 height, objects.py:112-114)
+ *   aspect_ratio   :17-23 (float32 extents and division; x/0 = inf, 0/0 = nan compare false; `size < 1.0` exemption)
+ *   volume         :25-35   area  :37-46: convex hull of xy with exact float64 orientation tests, shoelace area in float64
+ *                  (the reference: qhull + a float32 shoelace, pointcloud_utils.py:123-126), volume = area * float32 height;
+ *                  fewer than 3 points -> false; a degenerate hull (collinear / identical points: the reference dies with
+ *                  QhullError) -> area 0, verdict `0 >= min_area`, VG_FILTER_FLAG_DEGENERATE; more than 1024 hull vertices ->
+ *                  verdicts 0 and VG_FILTER_FLAG_HULL_OVERFLOW: the caller must compute that cluster's area itself
+ *   plane_distance :51-60   ephemeral_score :62-64: np.percentile(scores, percentile) (linear method: the two order statistics
+ *                  at floor(t(n-1)) and the next by an exact radix select, combined in float64), verdict `not (q > min score)`
+ * number_points, height and plane_distance use the arithmetic of vg_cluster_filter: the same bits through either entry.
+ * d_scores: float32 per ROW of d_points (indexed like d_points by d_index); may be NULL unless ephemeral_score is active.
+ * d_stats[c][VG_FILTER_NSTATS] (float64) = {n, zmin, zmax, dmin, dmax, height, size_x, size_y, aspect ratio, area, volume,
+ *   hull vertices, flags, percentile value, sum(|x_i y_j| + |x_j y_i|) over the hull edges, 0}
+ * d_verdict[c][VG_FILTER_COUNT]: every ACTIVE filter's own verdict (Detection.filter_dict), 0 for inactive ones;
+ * d_valid[c]: the combination. */
+#define VG_FILTER_NUMBER_POINTS 0
+#define VG_FILTER_HEIGHT 1
+#define VG_FILTER_ASPECT_RATIO 2
+#define VG_FILTER_VOLUME 3
+#define VG_FILTER_AREA 4
+#define VG_FILTER_PLANE_DISTANCE 5
+#define VG_FILTER_EPHEMERAL_SCORE 6
+#define VG_FILTER_COUNT 7
+#define VG_FILTER_NSTATS 16
+#define VG_FILTER_AND_REQUIRED 0   /* logic: and, required: True */
+#define VG_FILTER_AND 1            /* logic: and */
+#define VG_FILTER_OR 2             /* logic: or */
+#define VG_FILTER_FLAG_DEGENERATE 1
+#define VG_FILTER_FLAG_HULL_OVERFLOW 2
+typedef struct vg_filter_params {
+    int active[VG_FILTER_COUNT];
+    int logic[VG_FILTER_COUNT];
+    int min_points, max_points;
+    int has_max_volume, has_max_area;      /* cluster_utils.py:33,44: optional kwargs */
+    double min_height, max_height;
+    double min_aspect_ratio, max_aspect_ratio;
+    double min_volume, max_volume;
+    double min_area, max_area;
+    double max_min_height, min_max_height;
+    double percentile, min_percentile_pp_score;
+} vg_filter_params;
+void vg_filter_default_params(vg_filter_params* p);    /* nothing active, every threshold open */
+int vg_cluster_filter_ex(const float* d_points, int stride, const int32_t* d_index, const int32_t* d_seg_off, int n_clusters,
+                         const double* d_plane4, const float* d_scores, const vg_filter_params* p, double* d_stats,
+                         uint8_t* d_verdict, uint8_t* d_valid, void* stream);
+
 /* fit_bounding_boxes_simple, static branch (src/vilgod/zero_shot_detector.py:444-462) with
  * method minimum_bounding_rectangle (pointcloud_utils.py:309-372): d_box7[c] = {cx,cy,cz,l,w,h+0.3,rz} float64 in
  * the frame of d_points; d_aux3[c] = {hull vertices, rectangle area, degenerate flag}.  All hull edges are tried

@@ -71,6 +71,33 @@ def _load():
 lib = _load()
 
 
+# vg_cluster_filter_ex: column order of d_verdict / vg_filter_params.active (include/vilgod_hip.h VG_FILTER_*)
+FILTER_NAMES = ('filter_by_number_points', 'filter_by_height', 'filter_by_aspect_ratio', 'filter_by_volume', 'filter_by_area',
+                'filter_by_plane_distance', 'filter_by_ephemeral_score')
+FILTER_AND_REQUIRED, FILTER_AND, FILTER_OR = 0, 1, 2
+FILTER_NSTATS = 16
+FILTER_FLAG_DEGENERATE, FILTER_FLAG_HULL_OVERFLOW = 1, 2
+
+
+class FilterParams(ctypes.Structure):
+    """vg_filter_params (include/vilgod_hip.h), passed by reference to vg_cluster_filter_ex."""
+    _fields_ = [
+        ('active', ctypes.c_int * 7), ('logic', ctypes.c_int * 7),
+        ('min_points', ctypes.c_int), ('max_points', ctypes.c_int),
+        ('has_max_volume', ctypes.c_int), ('has_max_area', ctypes.c_int),
+        ('min_height', ctypes.c_double), ('max_height', ctypes.c_double),
+        ('min_aspect_ratio', ctypes.c_double), ('max_aspect_ratio', ctypes.c_double),
+        ('min_volume', ctypes.c_double), ('max_volume', ctypes.c_double),
+        ('min_area', ctypes.c_double), ('max_area', ctypes.c_double),
+        ('max_min_height', ctypes.c_double), ('min_max_height', ctypes.c_double),
+        ('percentile', ctypes.c_double), ('min_percentile_pp_score', ctypes.c_double),
+    ]
+
+    def __init__(self):
+        super().__init__()
+        lib.vg_filter_default_params(ctypes.byref(self))
+
+
 def ptr(t):
     """Device/host pointer of a torch tensor (or None)."""
     if t is None:

@@ -7,6 +7,8 @@
 //                      (un-vendored library + global RNG state: PARITY UNPINNED)
 //   k_cluster_filter   B4 + C1: per cluster n, z extent, signed plane distances -> the three active validity
 //                      filters (cluster_utils.py:14-15, 48-49, 51-60; objects.py:158-181)
+//   k_cluster_filter_ex  all seven filters of cluster_utils.py:14-64 (aspect ratio, hull area / volume, score percentile
+//                      too) with the and / or / required combination of objects.py:158-181
 //   k_cluster_box      E1: 2-D convex hull (gift wrapping with exact float64 orientation tests) + minimum-area
 //                      rectangle over the hull edges + the box assembly of zero_shot_detector.py:451-461.
 //                      Deviation (documented): ALL hull edges are tried; the reference drops the closing edge of
@@ -499,6 +501,233 @@ __global__ __launch_bounds__(256) void k_cluster_medians(const float* __restrict
     if (threadIdx.x == 0) out[(size_t)c * n_cols + col] = m;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Every filter of cluster_utils.py with Detection.filter's and / or / required combination (objects.py:158-181).
+// One workgroup per cluster, walking a persistent grid.  Per cluster: one pass for the float32 extents and the plane distances
+// (the arithmetic of k_cluster_filter), gift wrapping with vg_orient for the xy hull (only when area or volume is active), a
+// radix select on the scores (only when the ephemeral filter is active).  The hull's vertices and the select's staged keys share
+// one LDS buffer: the two phases do not overlap.
+#define FEX_HULL_CAP 1024
+#define FEX_KEY_CAP 4096
+__device__ __forceinline__ bool vg_hull_better(double cx0, double cy0, int bi, double bx, double by, double bd2,
+                                               int oi, double ox, double oy, double od2) {
+    // true when candidate o replaces the current best b as the next counter-clockwise vertex seen from (cx0, cy0)
+    if (oi < 0) return false;
+    if (bi < 0) return true;
+    const double orr = vg_orient(cx0, cy0, bx, by, ox, oy);
+    return orr < 0 || (orr == 0 && (od2 > bd2 || (od2 == bd2 && oi < bi)));
+}
+
+__global__ __launch_bounds__(256) void k_cluster_filter_ex(const float* __restrict__ pts, int stride,
+                                                           const int* __restrict__ index, const int* __restrict__ seg_off,
+                                                           int n_clusters, const double* __restrict__ plane,
+                                                           const float* __restrict__ scores, const vg_filter_params P,
+                                                           double* __restrict__ stats, unsigned char* __restrict__ verdict,
+                                                           unsigned char* __restrict__ valid) {
+    __shared__ double buf[2 * FEX_HULL_CAP];            // hx | hy, or FEX_KEY_CAP staged keys
+    __shared__ uint32_t hist[256];
+    __shared__ uint32_t sel[6];
+    __shared__ float rf[6][4];
+    __shared__ double rd[2][4];
+    __shared__ double red_x[4], red_y[4], red_d2[4];
+    __shared__ int red_i[4];
+    __shared__ int sh_cur, sh_start;
+    double* hx = buf;
+    double* hy = buf + FEX_HULL_CAP;
+    uint32_t* keys = reinterpret_cast<uint32_t*>(buf);
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const double a = plane[0], b = plane[1], cc = plane[2], d = plane[3];
+    const double inv = sqrt((a * a + b * b) + cc * cc);
+    const bool want_hull = P.active[VG_FILTER_AREA] || P.active[VG_FILTER_VOLUME];
+    const bool want_q = P.active[VG_FILTER_EPHEMERAL_SCORE] != 0;
+    for (int c = blockIdx.x; c < n_clusters; c += gridDim.x) {
+        const int p0 = seg_off[c], n = seg_off[c + 1] - p0;
+        const int* idx = index + p0;
+#define PX(i) ((double)pts[(size_t)idx[i] * stride])
+#define PY(i) ((double)pts[(size_t)idx[i] * stride + 1])
+        // ---- pass 1: float32 extents, plane distances, hull start vertex (lowest y, then lowest x, then lowest position) ----
+        float xmin = INFINITY, xmax = -INFINITY, ymin = INFINITY, ymax = -INFINITY, zmin = INFINITY, zmax = -INFINITY;
+        double dmin = INFINITY, dmax = -INFINITY;
+        for (int i = tid; i < n; i += 256) {
+            const float* p = pts + (size_t)idx[i] * stride;
+            xmin = fminf(xmin, p[0]); xmax = fmaxf(xmax, p[0]);
+            ymin = fminf(ymin, p[1]); ymax = fmaxf(ymax, p[1]);
+            zmin = fminf(zmin, p[2]); zmax = fmaxf(zmax, p[2]);
+            double dist = (((a * (double)p[0] + b * (double)p[1]) + cc * (double)p[2]) + d) / inv;
+            dmin = fmin(dmin, dist);
+            dmax = fmax(dmax, dist);
+        }
+        xmin = vg_wave_min(xmin); xmax = vg_wave_max(xmax);
+        ymin = vg_wave_min(ymin); ymax = vg_wave_max(ymax);
+        zmin = vg_wave_min(zmin); zmax = vg_wave_max(zmax);
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            dmin = fmin(dmin, __shfl_xor(dmin, o));
+            dmax = fmax(dmax, __shfl_xor(dmax, o));
+        }
+        if (lane == 0) {
+            rf[0][wv] = xmin; rf[1][wv] = xmax; rf[2][wv] = ymin; rf[3][wv] = ymax; rf[4][wv] = zmin; rf[5][wv] = zmax;
+            rd[0][wv] = dmin; rd[1][wv] = dmax;
+        }
+        __syncthreads();
+        xmin = fminf(fminf(rf[0][0], rf[0][1]), fminf(rf[0][2], rf[0][3]));
+        xmax = fmaxf(fmaxf(rf[1][0], rf[1][1]), fmaxf(rf[1][2], rf[1][3]));
+        ymin = fminf(fminf(rf[2][0], rf[2][1]), fminf(rf[2][2], rf[2][3]));
+        ymax = fmaxf(fmaxf(rf[3][0], rf[3][1]), fmaxf(rf[3][2], rf[3][3]));
+        zmin = fminf(fminf(rf[4][0], rf[4][1]), fminf(rf[4][2], rf[4][3]));
+        zmax = fmaxf(fmaxf(rf[5][0], rf[5][1]), fmaxf(rf[5][2], rf[5][3]));
+        dmin = fmin(fmin(rd[0][0], rd[0][1]), fmin(rd[0][2], rd[0][3]));
+        dmax = fmax(fmax(rd[1][0], rd[1][1]), fmax(rd[1][2], rd[1][3]));
+        const float height = zmax - zmin;                                  // objects.py:112-114 (float32)
+
+        // ---- convex hull of xy (cluster_utils.py:25-46), counter-clockwise from the lowest point ----
+        int nh = 0;
+        bool degenerate = false, overflow = false;
+        double area = 0.0, abs_sum = 0.0;
+        if (want_hull && n >= 3) {
+            // the lowest-y points all have y == ymin; among them the lowest x, then the first position
+            double bx = INFINITY;
+            int bi = -1;
+            for (int i = tid; i < n; i += 256) {
+                const double x = PX(i);
+                if (PY(i) == (double)ymin && (x < bx || bi < 0)) { bx = x; bi = i; }
+            }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                const double ox = __shfl_xor(bx, o);
+                const int oi = __shfl_xor(bi, o);
+                if (oi >= 0 && (bi < 0 || ox < bx || (ox == bx && oi < bi))) { bx = ox; bi = oi; }
+            }
+            if (lane == 0) { red_x[wv] = bx; red_i[wv] = bi; }
+            __syncthreads();
+            if (tid == 0) {
+                for (int k = 1; k < 4; ++k)
+                    if (red_i[k] >= 0 && (red_i[0] < 0 || red_x[k] < red_x[0] || (red_x[k] == red_x[0] && red_i[k] < red_i[0]))) {
+                        red_x[0] = red_x[k]; red_i[0] = red_i[k];
+                    }
+                sh_start = red_i[0];
+                sh_cur = red_i[0];
+            }
+            __syncthreads();
+            const int start = sh_start;
+            degenerate = start < 0;                                        // (no finite y: nothing to wrap)
+            const double sx0 = degenerate ? 0.0 : PX(start), sy0 = degenerate ? 0.0 : PY(start);
+            while (!degenerate) {
+                const int cur = sh_cur;
+                const double cx0 = PX(cur), cy0 = PY(cur);
+                if (nh >= FEX_HULL_CAP) { overflow = true; break; }       // uniform: nh is counted by every thread
+                if (tid == 0) { hx[nh] = cx0; hy[nh] = cy0; }
+                nh++;
+                int best = -1;
+                double bxx = 0, byy = 0, bd2 = -1;
+                for (int i = tid; i < n; i += 256) {
+                    const double x = PX(i), y = PY(i);
+                    if (x == cx0 && y == cy0) continue;                    // the current vertex itself and its duplicates
+                    const double d2 = (x - cx0) * (x - cx0) + (y - cy0) * (y - cy0);
+                    if (vg_hull_better(cx0, cy0, best, bxx, byy, bd2, i, x, y, d2)) { best = i; bxx = x; byy = y; bd2 = d2; }
+                }
+#pragma unroll
+                for (int o = 32; o > 0; o >>= 1) {
+                    const int oi = __shfl_xor(best, o);
+                    const double ox = __shfl_xor(bxx, o), oy = __shfl_xor(byy, o), od = __shfl_xor(bd2, o);
+                    if (vg_hull_better(cx0, cy0, best, bxx, byy, bd2, oi, ox, oy, od)) { best = oi; bxx = ox; byy = oy; bd2 = od; }
+                }
+                __syncthreads();                                           // every thread has read sh_cur
+                if (lane == 0) { red_i[wv] = best; red_x[wv] = bxx; red_y[wv] = byy; red_d2[wv] = bd2; }
+                __syncthreads();
+                if (tid == 0) {
+                    int bb = red_i[0];
+                    double x = red_x[0], y = red_y[0], d2 = red_d2[0];
+                    for (int k = 1; k < 4; ++k)
+                        if (vg_hull_better(cx0, cy0, bb, x, y, d2, red_i[k], red_x[k], red_y[k], red_d2[k])) {
+                            bb = red_i[k]; x = red_x[k]; y = red_y[k]; d2 = red_d2[k];
+                        }
+                    sh_cur = bb;
+                }
+                __syncthreads();
+                const int nxt = sh_cur;
+                if (nxt < 0) { degenerate = true; break; }                 // all points coincide
+                if (PX(nxt) == sx0 && PY(nxt) == sy0) break;               // closed
+            }
+            __syncthreads();                                               // hx / hy of the last vertex are visible
+            if (!degenerate && !overflow) {
+                // shoelace in float64 (products of float32 values are exact); every thread computes the same serial sum
+                double a2 = 0.0;
+                for (int i = 0; i < nh; ++i) {
+                    const int j = i + 1 == nh ? 0 : i + 1;
+                    const double t0 = hx[i] * hy[j], t1 = hx[j] * hy[i];
+                    a2 += t0 - t1;
+                    abs_sum += fabs(t0) + fabs(t1);
+                }
+                area = 0.5 * fabs(a2);
+                if (nh < 3 || !(area > 0.0)) { degenerate = true; area = 0.0; }
+            } else if (degenerate) {
+                area = 0.0;
+            }
+        }
+        const double volume = area * (double)height;                       // cluster_utils.py:30 (float64 here)
+
+        // ---- percentile of the scores (cluster_utils.py:62-64; numpy's linear method) ----
+        double q = 0.0;
+        if (want_q && n > 0) {
+            __syncthreads();                                               // the hull buffer becomes the key buffer
+            const double virt = (P.percentile / 100.0) * (double)(n - 1);
+            int lo = (int)floor(virt);
+            lo = lo < 0 ? 0 : (lo > n - 1 ? n - 1 : lo);
+            const double g = virt - (double)lo;
+            const int hi = lo + 1 < n ? lo + 1 : n - 1;
+            float va, vb;
+            if (n <= FEX_KEY_CAP) {
+                for (int i = tid; i < n; i += 256) keys[i] = vg_fkey(scores[idx[i]]);
+                __syncthreads();
+                va = vg_select_keys<true>(scores, 1, 0, idx, keys, n, lo, hist, sel);
+                vb = hi == lo ? va : vg_select_keys<true>(scores, 1, 0, idx, keys, n, hi, hist, sel);
+            } else {
+                va = vg_select_keys<false>(scores, 1, 0, idx, keys, n, lo, hist, sel);
+                vb = hi == lo ? va : vg_select_keys<false>(scores, 1, 0, idx, keys, n, hi, hist, sel);
+            }
+            const double A = (double)va, B = (double)vb, dd = B - A;
+            q = g >= 0.5 ? B - dd * (1.0 - g) : A + dd * g;               // frame_state.static_from_entropy
+        }
+
+        if (tid == 0) {
+            unsigned char v[VG_FILTER_COUNT];
+            v[VG_FILTER_NUMBER_POINTS] = n >= P.min_points && n <= P.max_points;                          // cluster_utils.py:14-15
+            v[VG_FILTER_HEIGHT] = (double)height >= P.min_height && (double)height <= P.max_height;        // :48-49
+            v[VG_FILTER_PLANE_DISTANCE] = dmin <= P.max_min_height && dmax >= P.min_max_height;            // :58-60
+            const float sx = xmax - xmin, sy = ymax - ymin;                                                // :18 (float32)
+            const float ratio = fmaxf(sx, sy) / fminf(sx, sy);                                             // :20 (x/0 = inf, 0/0 = nan)
+            v[VG_FILTER_ASPECT_RATIO] = (((double)ratio >= P.min_aspect_ratio) || sx < 1.0f || sy < 1.0f) &&
+                                        ((double)ratio <= P.max_aspect_ratio);                             // :20-23
+            bool okv = n >= 3 && !overflow && volume >= P.min_volume;                                      // :26-34
+            if (P.has_max_volume) okv = okv && volume <= P.max_volume;
+            bool oka = n >= 3 && !overflow && area >= P.min_area;                                          // :37-46
+            if (P.has_max_area) oka = oka && area <= P.max_area;
+            v[VG_FILTER_VOLUME] = okv;
+            v[VG_FILTER_AREA] = oka;
+            v[VG_FILTER_EPHEMERAL_SCORE] = !(q > P.min_percentile_pp_score);                               // :64
+            // objects.py:181: (all(and) or any(or)) and all(and_required); all([]) = True, any([]) = False
+            bool all_and = true, any_or = false, all_req = true;
+            for (int k = 0; k < VG_FILTER_COUNT; ++k) {
+                if (!P.active[k]) { v[k] = 0; continue; }
+                if (P.logic[k] == VG_FILTER_AND_REQUIRED) all_req = all_req && v[k];
+                else if (P.logic[k] == VG_FILTER_AND) all_and = all_and && v[k];
+                else any_or = any_or || v[k];
+            }
+            for (int k = 0; k < VG_FILTER_COUNT; ++k) verdict[(size_t)c * VG_FILTER_COUNT + k] = v[k];
+            valid[c] = ((all_and || any_or) && all_req) ? 1 : 0;
+            double* s = stats + (size_t)c * VG_FILTER_NSTATS;
+            s[0] = (double)n; s[1] = (double)zmin; s[2] = (double)zmax; s[3] = dmin; s[4] = dmax; s[5] = (double)height;
+            s[6] = (double)sx; s[7] = (double)sy; s[8] = (double)ratio; s[9] = area; s[10] = volume; s[11] = (double)nh;
+            s[12] = (double)((degenerate ? VG_FILTER_FLAG_DEGENERATE : 0) | (overflow ? VG_FILTER_FLAG_HULL_OVERFLOW : 0));
+            s[13] = q; s[14] = abs_sum; s[15] = 0.0;
+        }
+        __syncthreads();                                                   // the next cluster reuses every shared array
+#undef PX
+#undef PY
+    }
+}
+
 extern "C" {
 
 int vg_cluster_medians(const float* d_points, int stride, int n_cols, const int32_t* d_index, const int32_t* d_seg_off, int n_clusters,
@@ -544,6 +773,33 @@ int vg_cluster_filter(const float* d_points, int stride, const int32_t* d_index,
     if (!d_points || !d_index || !d_seg_off || !d_plane4 || !d_stats6 || !d_valid) return VG_ERR_ARG;
     hipLaunchKernelGGL(k_cluster_filter, dim3(n_clusters), dim3(256), 0, (hipStream_t)stream, d_points, stride, d_index, d_seg_off,
                        d_plane4, min_points, max_points, max_min_height, min_max_height, min_height, max_height, d_stats6, d_valid);
+    VG_LAUNCH_CHECK();
+    return VG_OK;
+}
+
+void vg_filter_default_params(vg_filter_params* p) {
+    memset(p, 0, sizeof(*p));
+    p->min_points = 0;                       // cluster_utils.py:14
+    p->max_points = 999999;
+    p->min_height = -1e300; p->max_height = 1e300;
+    p->min_aspect_ratio = -1e300; p->max_aspect_ratio = 1e300;
+    p->min_volume = -1e300; p->max_volume = 1e300;
+    p->min_area = -1e300; p->max_area = 1e300;
+    p->max_min_height = 1e300; p->min_max_height = -1e300;
+    p->percentile = 50.0; p->min_percentile_pp_score = 1e300;
+}
+
+int vg_cluster_filter_ex(const float* d_points, int stride, const int32_t* d_index, const int32_t* d_seg_off, int n_clusters,
+                         const double* d_plane4, const float* d_scores, const vg_filter_params* p, double* d_stats,
+                         uint8_t* d_verdict, uint8_t* d_valid, void* stream) {
+    if (n_clusters <= 0) return VG_OK;
+    if (!d_points || !d_index || !d_seg_off || !d_plane4 || !p || !d_stats || !d_verdict || !d_valid || stride < 3) return VG_ERR_ARG;
+    for (int k = 0; k < VG_FILTER_COUNT; ++k)
+        if (p->active[k] && (p->logic[k] < VG_FILTER_AND_REQUIRED || p->logic[k] > VG_FILTER_OR)) return VG_ERR_ARG;
+    if (p->active[VG_FILTER_EPHEMERAL_SCORE] && (!d_scores || !(p->percentile >= 0.0 && p->percentile <= 100.0))) return VG_ERR_ARG;
+    const int grid = n_clusters < 2048 ? n_clusters : 2048;          // 256 CUs x 8 resident workgroups: larger lists walk the grid
+    hipLaunchKernelGGL(k_cluster_filter_ex, dim3(grid), dim3(256), 0, (hipStream_t)stream, d_points, stride, d_index, d_seg_off,
+                       n_clusters, d_plane4, d_scores, *p, d_stats, d_verdict, d_valid);
     VG_LAUNCH_CHECK();
     return VG_OK;
 }

@@ -134,6 +134,8 @@ class FrameState:
         self.boxes = None                              # [C,7] float64 ref frame, NaN rows = no box
         self.cls = {}                                  # key -> dict(pred, detailed, score [C,V]; name, final [C]; has [C])
         self.filtered = False
+        self.filter_dict = {}                          # Detection.filter_dict (objects.py:168), name -> bool [C]: every active filter's own
+                                                       # verdict, written only when vg_cluster_filter_ex ran (not serialised, like the reference)
 
     @property
     def n_detections(self):

@@ -14,6 +14,7 @@ benchmark can call them one by one; `process_frame` chains them.
     results                        F1      host numpy
 """
 import contextlib
+import ctypes
 import os
 import threading
 import time
@@ -22,7 +23,8 @@ import numpy as np
 import torch
 from scipy.spatial.transform import Rotation
 
-from ._lib import lib, ptr, stream_ptr, check
+from ._lib import (lib, ptr, stream_ptr, check, FilterParams, FILTER_NAMES, FILTER_AND_REQUIRED, FILTER_AND, FILTER_OR, FILTER_NSTATS,
+                   FILTER_FLAG_HULL_OVERFLOW)
 from .frame_state import FrameState, pack_clusters, vote, static_from_entropy
 from . import patchworkpp as gpw
 from .hdbscan import HDBSCAN
@@ -53,6 +55,42 @@ def default_preprocessor_cfg():
         clip=dict(name='clip', model_name='ViT-B-16.pt', top_k=1, split_size=50,
                   prompt_template='a point representation of a {}', class_list=DEFAULT_CLASS_LIST,
                   class_mapping=DEFAULT_CLASS_MAPPING))
+
+
+def host_hull_area(xy):
+    """float64 shoelace area of the convex hull of float32 xy (the filter kernel's fallback for hulls beyond its capacity) -> area,
+    hull vertices.  Products of float32 values are exact in float64; the terms are summed exactly (math.fsum)."""
+    import math
+    from scipy import spatial
+    xy = np.asarray(xy, np.float64)
+    try:
+        v = spatial.ConvexHull(xy).vertices
+    except spatial.QhullError:
+        return 0.0, 0
+    x, y = xy[v, 0], xy[v, 1]
+    xn, yn = np.roll(x, -1), np.roll(y, -1)
+    return 0.5 * abs(math.fsum(np.concatenate([x * yn, -(xn * y)]))), len(v)
+
+
+def combine_verdicts(verdict, P):
+    """objects.py:181 on a [C,7] bool matrix: (all(and) or any(or)) and all(and + required); all([]) = True, any([]) = False."""
+    C = verdict.shape[0]
+    all_and, any_or, all_req = np.ones(C, bool), np.zeros(C, bool), np.ones(C, bool)
+    for k in range(len(FILTER_NAMES)):
+        if not P.active[k]:
+            continue
+        if P.logic[k] == FILTER_AND_REQUIRED:
+            all_req &= verdict[:, k]
+        elif P.logic[k] == FILTER_AND:
+            all_and &= verdict[:, k]
+        else:
+            any_or |= verdict[:, k]
+    return (all_and | any_or) & all_req
+
+
+def _open(v, big=1e300):
+    """a threshold as the kernels take it: float64, infinities clamped (an unencodable 64-bit literal otherwise; build.check_isa)"""
+    return float(min(max(float(v), -big), big))
 
 
 def _get(cfg, key, default=None):
@@ -337,29 +375,64 @@ class PseudoLabelPipeline:
 
     @staticmethod
     def _parse_filters(ccfg):
+        """clustering.filters / filters_active -> thresholds, the active filters in the order of the config with their combination
+        class, and which entry point runs them.  zero_shot_detector.py:279-286: a filter runs when its name is in `filters_active`
+        AND cluster_utils defines it (filter_by_density is skipped silently); objects.py:164-175: its `logic` must be and | or."""
         active = list(_get(ccfg, 'filters_active', []))
         f = dict(min_points=0, max_points=999999, max_min_height=np.inf, min_max_height=-np.inf, min_height=-np.inf,
-                 max_height=np.inf, use_plane=False)
-        known = {'filter_by_number_points', 'filter_by_plane_distance', 'filter_by_height'}
+                 max_height=np.inf, use_plane=False, active=[], logic={})
+        P = FilterParams()
         for flt in _get(ccfg, 'filters', []):
             name, args = _get(flt, 'name'), dict(_get(flt, 'args', {}))
-            if name not in active:
+            if name not in active or name not in FILTER_NAMES:
                 continue
-            if name not in known:
-                # zero_shot_detector.py:283: filters that do not exist in cluster_utils are skipped silently
-                # (filter_by_density); the others of cluster_utils are not used by the shipped configs
-                if name in ('filter_by_aspect_ratio', 'filter_by_volume', 'filter_by_area', 'filter_by_ephemeral_score'):
-                    raise NotImplementedError(f'{name} is not active in the reference configs and has no GPU kernel')
-                continue
-            if not (args.get('logic') == 'and' and args.get('required', False)):
-                raise NotImplementedError('only `logic: and, required: True` filters (the shipped configuration)')
+            logic, required = args.get('logic'), bool(args.get('required', False))
+            if logic not in ('and', 'or'):
+                raise ValueError(f'Logic for filter {name} not defined!')              # objects.py:175
+            k = FILTER_NAMES.index(name)
+            if name not in f['active']:
+                f['active'].append(name)
+            f['logic'][name] = (logic, required)
+            P.active[k] = 1
+            P.logic[k] = FILTER_OR if logic == 'or' else (FILTER_AND_REQUIRED if required else FILTER_AND)
             if name == 'filter_by_number_points':
                 f['min_points'], f['max_points'] = args.get('min_points', 0), args.get('max_points', 999999)
+                P.min_points, P.max_points = int(f['min_points']), int(f['max_points'])
             elif name == 'filter_by_height':
                 f['min_height'], f['max_height'] = args['min_height'], args['max_height']
-            else:
+                P.min_height, P.max_height = _open(f['min_height']), _open(f['max_height'])
+            elif name == 'filter_by_plane_distance':
                 f['max_min_height'], f['min_max_height'], f['use_plane'] = args['max_min_height'], args['min_max_height'], True
+                P.max_min_height, P.min_max_height = _open(f['max_min_height']), _open(f['min_max_height'])
+            elif name == 'filter_by_aspect_ratio':
+                P.min_aspect_ratio, P.max_aspect_ratio = _open(args['min_aspect_ratio']), _open(args['max_aspect_ratio'])
+            elif name == 'filter_by_volume':
+                P.min_volume = _open(args['min_volume'])
+                if args.get('max_volume', None) is not None:                           # cluster_utils.py:33
+                    P.has_max_volume, P.max_volume = 1, _open(args['max_volume'])
+            elif name == 'filter_by_area':
+                P.min_area = _open(args['min_area'])
+                if args.get('max_area', None) is not None:                             # cluster_utils.py:44
+                    P.has_max_area, P.max_area = 1, _open(args['max_area'])
+            else:
+                P.percentile, P.min_percentile_pp_score = float(args['percentile']), _open(args['min_percentile_pp_score'])
+                if not 0.0 <= P.percentile <= 100.0:
+                    raise ValueError('filter_by_ephemeral_score: percentile must be in [0, 100]')
+        shipped = {'filter_by_number_points', 'filter_by_plane_distance', 'filter_by_height'}
+        # the shipped set (all `and` + `required`) keeps its own kernel; every other set runs vg_cluster_filter_ex
+        f['entry'] = 'vg_cluster_filter' if set(f['active']) == shipped and all(v == ('and', True) for v in f['logic'].values()) \
+            else 'vg_cluster_filter_ex'
+        f['needs_entropy'] = 'filter_by_ephemeral_score' in f['active']
+        f['params'] = P
         return f
+
+    @staticmethod
+    def check_filter_stages(filters, pipeline_active):
+        """filter_by_ephemeral_score reads the per-point entropy scores: a run that filters without the stage that computes them
+        cannot work (the reference would fail in np.percentile(None) at the first detection)."""
+        if filters['needs_entropy'] and 'filter_detections' in pipeline_active and 'calculate_entropy_scores' not in pipeline_active:
+            raise ValueError('filter_by_ephemeral_score is active but the stage calculate_entropy_scores is not in pipeline_active '
+                             '(keep it listed on a resumed run too: it skips frames that already hold their scores)')
 
     # ---------------------------------------------------------------------------------------------
     def _mark(self, name):
@@ -441,18 +514,63 @@ class PseudoLabelPipeline:
         return p
 
     # [B4] + [C1]
-    def filter(self, d_X, d_index, d_seg, plane):
+    def filter(self, d_X, d_index, d_seg, plane, entropy=None):
+        """-> valid [C] uint8, stats [C,6] float32 (device).  The shipped filter set runs vg_cluster_filter; any other set runs
+        vg_cluster_filter_ex and leaves every active filter's own verdict in `self.last_filter_dict` (name -> bool [C], host;
+        None after the shipped entry) and the kernel's full statistics in `self.last_filter_stats`.
+        entropy: float32 score per row of d_X (host array or device tensor), read by filter_by_ephemeral_score only."""
         C = d_seg.numel() - 1
-        stats = torch.empty((C, 6), dtype=torch.float32, device=self.device)
-        valid = torch.empty(C, dtype=torch.uint8, device=self.device)
         f = self._filters
         d_plane = torch.from_numpy(np.ascontiguousarray(plane, dtype=np.float64)).to(self.device)
-        big = 1e300
-        check(lib.vg_cluster_filter(ptr(d_X), d_X.stride(0), ptr(d_index), ptr(d_seg), C, ptr(d_plane), int(f['min_points']),
-                                    int(f['max_points']), float(min(f['max_min_height'], big)), float(max(f['min_max_height'], -big)),
-                                    float(max(f['min_height'], -big)), float(min(f['max_height'], big)), ptr(stats), ptr(valid),
-                                    stream_ptr()), 'vg_cluster_filter')
-        return valid, stats
+        self.last_filter_dict = self.last_filter_stats = None
+        if f['entry'] == 'vg_cluster_filter':
+            stats = torch.empty((C, 6), dtype=torch.float32, device=self.device)
+            valid = torch.empty(C, dtype=torch.uint8, device=self.device)
+            big = 1e300
+            check(lib.vg_cluster_filter(ptr(d_X), d_X.stride(0), ptr(d_index), ptr(d_seg), C, ptr(d_plane), int(f['min_points']),
+                                        int(f['max_points']), float(min(f['max_min_height'], big)), float(max(f['min_max_height'], -big)),
+                                        float(max(f['min_height'], -big)), float(min(f['max_height'], big)), ptr(stats), ptr(valid),
+                                        stream_ptr()), 'vg_cluster_filter')
+            return valid, stats
+        d_ent = None
+        if f['needs_entropy']:
+            if entropy is None:
+                raise ValueError('filter_by_ephemeral_score is active but the frame has no entropy scores: run the stage '
+                                 'calculate_entropy_scores first (process_sequence computes them; process_frame cannot)')
+            d_ent = entropy if isinstance(entropy, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(entropy, dtype=np.float32))
+            d_ent = d_ent.to(self.device, dtype=torch.float32).contiguous()
+            if d_ent.numel() != d_X.shape[0]:
+                raise ValueError(f'entropy scores: {d_ent.numel()} values for {d_X.shape[0]} points')
+        P = f['params']
+        stats = torch.empty((C, FILTER_NSTATS), dtype=torch.float64, device=self.device)
+        verdict = torch.empty((C, len(FILTER_NAMES)), dtype=torch.uint8, device=self.device)
+        valid = torch.empty(C, dtype=torch.uint8, device=self.device)
+        check(lib.vg_cluster_filter_ex(ptr(d_X), d_X.stride(0), ptr(d_index), ptr(d_seg), C, ptr(d_plane), ptr(d_ent), ctypes.byref(P),
+                                       ptr(stats), ptr(verdict), ptr(valid), stream_ptr()), 'vg_cluster_filter_ex')
+        h_verdict = verdict.cpu().numpy().astype(bool)
+        if P.active[FILTER_NAMES.index('filter_by_area')] or P.active[FILTER_NAMES.index('filter_by_volume')]:
+            h_stats = stats.cpu().numpy()
+            over = np.flatnonzero(h_stats[:, 12].astype(np.int64) & FILTER_FLAG_HULL_OVERFLOW)
+            if len(over):
+                # hulls beyond the kernel's LDS capacity (1024 vertices; a dense ring): their area comes from the host
+                self._filter_overflow(d_X, d_index, d_seg, over, h_stats, h_verdict)
+                stats = torch.from_numpy(h_stats).to(self.device)
+                valid = torch.from_numpy(combine_verdicts(h_verdict, P).astype(np.uint8)).to(self.device)
+        self.last_filter_dict = {name: h_verdict[:, FILTER_NAMES.index(name)].copy() for name in f['active']}
+        self.last_filter_stats = stats
+        return valid, stats[:, :6].to(torch.float32)
+
+    def _filter_overflow(self, d_X, d_index, d_seg, rows, h_stats, h_verdict):
+        P = self._filters['params']
+        index, seg = d_index.cpu().numpy(), d_seg.cpu().numpy()
+        for c in rows:
+            xy = d_X[torch.from_numpy(index[seg[c]:seg[c + 1]].astype(np.int64)).to(self.device), :2].cpu().numpy()
+            area, nh = host_hull_area(xy)
+            volume = area * h_stats[c, 5]
+            h_stats[c, 9], h_stats[c, 10], h_stats[c, 11] = area, volume, nh
+            ka, kv = FILTER_NAMES.index('filter_by_area'), FILTER_NAMES.index('filter_by_volume')
+            h_verdict[c, ka] = bool(P.active[ka]) and area >= P.min_area and (not P.has_max_area or area <= P.max_area)
+            h_verdict[c, kv] = bool(P.active[kv]) and volume >= P.min_volume and (not P.has_max_volume or volume <= P.max_volume)
 
     # [D1]-[D9]
     def classify(self, d_X, d_index, d_seg, transform_to_ego):
@@ -765,8 +883,10 @@ class PseudoLabelPipeline:
             xy_host, xy_ev = self.xy_to_host_async(d_X)            # lands while the plane fit / filters / classification run
         plane = self.ground_plane(d_ref, gidx) if self._filters['use_plane'] else np.array([0.0, 0.0, 1.0, 0.0])
         fs.ground_plane_model_ref = plane
-        valid, stats = self.filter(d_X, d_index, d_seg, plane)
+        valid, stats = self.filter(d_X, d_index, d_seg, plane, entropy=entropy)
         fs.valid = valid.cpu().numpy().astype(bool)
+        if self.last_filter_dict is not None:
+            fs.filter_dict = self.last_filter_dict
         st = stats.cpu().numpy() if self.box_mode == 'reference' else None     # (the same kernel wrote it: no further wait)
         fs.filtered = True
         self._mark('plane+filter')

@@ -178,6 +178,8 @@ class ZeroShotDetector:
                                    angle_mode=dev.get('angle_mode', 'reference'), vit_graph=bool(dev.get('vit_graph', False)),
                                            hierarchy=dev.get('hierarchy', None))
         self.pipe = pipeline
+        if 'needs_entropy' in getattr(pipeline, '_filters', {}):
+            PseudoLabelPipeline.check_filter_stages(pipeline._filters, list(cfg.pipeline_active))
         self.sequence_data_dir_path = Path(cfg.paths.sequence_data)
         self.my_frames = vdist.shard_frames(self.lenght, self.rank, self.world_size)
         self.lidar_frame_list = []
@@ -685,8 +687,11 @@ class ZeroShotDetector:
         else:
             fs.ground_plane_model_ref = np.array([0.0, 0.0, 1.0, 0.0])
         d_index, d_seg = self._cluster_lists(fnr)
-        valid, _ = p.filter(X, d_index, d_seg, fs.ground_plane_model_ref)
+        ent = self._entropy_full(fnr) if p._filters['needs_entropy'] else None      # (None: p.filter raises, naming the stage)
+        valid, _ = p.filter(X, d_index, d_seg, fs.ground_plane_model_ref, entropy=ent)
         fs.valid = valid.cpu().numpy().astype(bool)
+        if p.last_filter_dict is not None:
+            fs.filter_dict = p.last_filter_dict
         fs.filtered = True
         self._box_prefetch.pop(fnr, None)                                        # (a request keyed on the previous valid rows)
 
