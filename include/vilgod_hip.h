@@ -274,6 +274,37 @@ int vg_hdbscan_tree_device(vg_hier* h, const int32_t* d_lo, const int32_t* d_hi,
 int vg_pack_clusters_host(const int32_t* h_labels, const double* h_probs, int n, double threshold, int64_t* h_ids,
                           int32_t* h_index, int32_t* h_seg, int32_t* h_n_clusters);
 
+/* The same grouping ON THE DEVICE (csrc/pack.hip), for labels that are born there (vg_hdbscan_tree_device) and lists that are only read
+ * there (vg_cluster_filter[_ex], vg_plane_ransac, vg_render_crops, vg_cluster_boxes / _lshape / _medians): lidar_frame.py:163-167 (low
+ * probability -> noise) and :230-237 (one Detection per remaining label, np.where's ascending indices) without leaving HBM.
+ * A point is dropped iff label < 0 or (d_probs given and prob < threshold: strict, float64, so a NaN probability keeps the point like
+ * numpy's `labels[probs < threshold] = -1`).  label_bound: exclusive upper bound of the labels, 0 .. 2^24 (a hierarchy of n points with
+ * min_cluster_size m selects at most n / m clusters); only the bits it needs are sorted.  n <= 2^24.
+ * Device outputs with vg_pack_clusters_host's meaning -- d_ids [capacity n] int64 labels that own a point, ascending; d_index
+ * [capacity n] kept point indices, cluster after cluster, ascending inside a cluster; d_seg [capacity n + 1] offsets -- and
+ * d_counts [3] = {C, P = d_seg[C], overflow}.  Only d_ids[0 .. C), d_index[0 .. P), d_seg[0 .. C] are written.  overflow != 0: some label
+ * was >= label_bound; those points were left out (nothing is written out of bounds) and the lists must not be used -- pack such a frame
+ * with a larger bound or with vg_pack_clusters_host.
+ * A fixed sequence of 3 * passes + 3 kernels and one 16-byte memset on `stream` (passes = 1, 2, 3 for label_bound <= 2^8, 2^16, 2^24):
+ * no host work, no synchronisation, no allocation.  A stable radix sort whose positions come from ranks, never from an atomic cursor:
+ * the same bits on every run.  d_work: vg_pack_clusters_work_bytes(n) bytes of device scratch (-1 for an n out of range), contents
+ * irrelevant before and after; one call at a time per work buffer.  VG_ERR_ARG (nothing launched, outputs untouched) for null pointers,
+ * n or label_bound out of range, work_bytes too small.  n == 0 / no kept point: C = P = 0, d_seg[0] = 0. */
+int64_t vg_pack_clusters_work_bytes(int n);
+int vg_pack_clusters(const int32_t* d_labels, const double* d_probs, int n, double threshold, int label_bound, void* d_work,
+                     int64_t work_bytes, int64_t* d_ids, int32_t* d_index, int32_t* d_seg, int32_t* d_counts, void* stream);
+
+/* The packed sub-lists of the clusters that passed the filters (classification and boxes are `valid_only`,
+ * src/vilgod/zero_shot_detector.py:389-390, :444-448): the segments c of (d_index, d_seg [n_clusters + 1]) with d_valid[c] != 0 --
+ * the bytes vg_cluster_filter / vg_cluster_filter_ex write, taken as they are -- concatenated in order.  n_index: entries of d_index
+ * the caller vouches for (P, or an upper bound of it: min(n_index, d_seg[n_clusters]) points are looked at).
+ * d_out_index [capacity n_index], d_out_seg [capacity n_clusters + 1], d_counts [2] = {kept clusters K, kept points Q}; only
+ * d_out_index[0 .. Q) and d_out_seg[0 .. K] are written.  Two kernels on `stream` (one scan of the cluster sizes, one copy that finds
+ * each point's cluster by bisection), deterministic.  d_work: vg_pack_select_work_bytes(n_clusters) bytes of device scratch. */
+int64_t vg_pack_select_work_bytes(int n_clusters);
+int vg_pack_select(const int32_t* d_index, const int32_t* d_seg, int n_clusters, int n_index, const uint8_t* d_valid, void* d_work,
+                   int64_t work_bytes, int32_t* d_out_index, int32_t* d_out_seg, int32_t* d_counts, void* stream);
+
 /* GPU half of the clustering: exact k-NN core distances and THE minimum spanning tree of the mutual
  * reachability graph under the strict edge order (w2, pair d2, min id, max id) (unique -> identical to the CPU oracle's). */
 typedef struct vg_cluster vg_cluster;

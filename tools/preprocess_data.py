@@ -93,7 +93,8 @@ def main(argv=None):
                                    min_range=ga['min_range'], z_offset=ga['z_offset'], plane_seed=dev.get('plane_seed', 666),
                                    box_mode=dev.get('box_mode', 'reference'), box_workers=dev.get('box_workers', 4),
                                    angle_mode=dev.get('angle_mode', 'reference'), vit_graph=bool(dev.get('vit_graph', False)),
-                                   cu_reserve=int(dev.get('cu_reserve', 0)), cu_tower=dev.get('cu_tower', 'complement'))
+                                   cu_reserve=int(dev.get('cu_reserve', 0)), cu_tower=dev.get('cu_tower', 'complement'),
+                                   pack=dev.get('pack', 'host'))
     logger.info(f'CLIP weights: {pipeline.clip.weights_source}')
     from vilgod_amd import clip_weights
     tc = pipeline.clip.encoder.cfg

@@ -55,6 +55,79 @@ def pack_clusters_numpy(labels, probs, threshold):
     return sl[starts].astype(np.int64), order.astype(np.int32), seg
 
 
+PACK_MAX_LABEL_BOUND = 1 << 24      # include/vilgod_hip.h vg_pack_clusters: label_bound and n go up to 2^24
+_PACK_WORK = {}                     # (device, stream) -> work buffer of pack_clusters_device / select_clusters_device callers without their own
+
+
+def _pack_work(nbytes, device, work):
+    """A work buffer of at least nbytes: the caller's, or one kept per (device, current stream) -- calls on one stream are ordered."""
+    import torch
+    if work is not None:
+        if work.numel() * work.element_size() < nbytes:
+            raise ValueError(f'work buffer: {work.numel() * work.element_size()} bytes, {nbytes} needed')
+        return work
+    key = (str(device), torch.cuda.current_stream(device).cuda_stream)
+    w = _PACK_WORK.get(key)
+    if w is None or w.numel() < nbytes:
+        w = _PACK_WORK[key] = torch.empty(max(int(nbytes), 1 << 16), dtype=torch.uint8, device=device)
+    return w
+
+
+def pack_clusters_device(d_labels, d_probs, threshold, label_bound=None, work=None, out=None):
+    """`pack_clusters` on the device (csrc/pack.hip vg_pack_clusters): d_labels CUDA int32 [n], d_probs CUDA float64 [n] or None.
+    label_bound: exclusive upper bound of the labels (default n: a partition of n points has at most n parts).
+    -> (ids int64 [n], index int32 [n], seg int32 [n + 1], counts int32 [3]) CUDA tensors, queued on the current stream, nothing waited
+    for.  counts = (C, P, overflow); the lists are ids[:C], index[:P], seg[:C + 1], the rest is not written; overflow != 0: a label was
+    >= label_bound and the lists must not be used.  work: uint8 CUDA scratch of vg_pack_clusters_work_bytes(n) bytes (default: one kept
+    per stream); out: (ids, index, seg, counts) tensors to write into."""
+    import torch
+    from ._lib import lib, check, ptr, stream_ptr
+    if not (d_labels.is_cuda and d_labels.dtype == torch.int32 and d_labels.dim() == 1 and d_labels.is_contiguous()):
+        raise ValueError('d_labels: contiguous CUDA int32 [n]')
+    n = d_labels.numel()
+    if d_probs is not None and not (d_probs.is_cuda and d_probs.dtype == torch.float64 and d_probs.is_contiguous() and d_probs.numel() == n):
+        raise ValueError('d_probs: contiguous CUDA float64 [n]')
+    dev = d_labels.device
+    bound = n if label_bound is None else int(label_bound)
+    nbytes = lib.vg_pack_clusters_work_bytes(n)
+    if nbytes < 0:
+        raise ValueError(f'vg_pack_clusters: {n} points (at most {PACK_MAX_LABEL_BOUND})')
+    work = _pack_work(nbytes, dev, work)
+    if out is None:
+        out = (torch.empty(n, dtype=torch.int64, device=dev), torch.empty(n, dtype=torch.int32, device=dev),
+               torch.empty(n + 1, dtype=torch.int32, device=dev), torch.empty(3, dtype=torch.int32, device=dev))
+    ids, index, seg, counts = out
+    check(lib.vg_pack_clusters(ptr(d_labels), ptr(d_probs), n, float(threshold), bound, ptr(work), work.numel(), ptr(ids), ptr(index),
+                               ptr(seg), ptr(counts), stream_ptr()), 'vg_pack_clusters')
+    return ids, index, seg, counts
+
+
+def select_clusters_device(d_index, d_seg, n_clusters, d_valid, n_index=None, work=None, out=None):
+    """The packed sub-lists of the clusters with d_valid[c] != 0 (csrc/pack.hip vg_pack_select): d_index CUDA int32, d_seg CUDA int32
+    [>= n_clusters + 1], d_valid CUDA uint8 [n_clusters] as the filter kernels write it.  n_index: entries of d_index (default: its
+    length).  -> (out_index int32 [n_index], out_seg int32 [n_clusters + 1], counts int32 [2] = kept clusters K, kept points Q) CUDA
+    tensors, queued on the current stream; only out_index[:Q] and out_seg[:K + 1] are written."""
+    import torch
+    from ._lib import lib, check, ptr, stream_ptr
+    C = int(n_clusters)
+    n_index = d_index.numel() if n_index is None else int(n_index)
+    if not (d_index.is_cuda and d_index.dtype == torch.int32 and d_index.is_contiguous() and d_index.numel() >= n_index):
+        raise ValueError('d_index: contiguous CUDA int32 [>= n_index]')
+    if not (d_seg.is_cuda and d_seg.dtype == torch.int32 and d_seg.is_contiguous() and d_seg.numel() >= C + 1):
+        raise ValueError('d_seg: contiguous CUDA int32 [>= n_clusters + 1]')
+    if not (d_valid.is_cuda and d_valid.dtype == torch.uint8 and d_valid.is_contiguous() and d_valid.numel() >= C):
+        raise ValueError('d_valid: contiguous CUDA uint8 [n_clusters]')
+    dev = d_index.device
+    work = _pack_work(lib.vg_pack_select_work_bytes(C), dev, work)
+    if out is None:
+        out = (torch.empty(n_index, dtype=torch.int32, device=dev), torch.empty(C + 1, dtype=torch.int32, device=dev),
+               torch.empty(2, dtype=torch.int32, device=dev))
+    o_index, o_seg, counts = out
+    check(lib.vg_pack_select(ptr(d_index), ptr(d_seg), C, n_index, ptr(d_valid), ptr(work), work.numel(), ptr(o_index), ptr(o_seg),
+                             ptr(counts), stream_ptr()), 'vg_pack_select')
+    return o_index, o_seg, counts
+
+
 def vote(class_ids, scores, class_names_sorted):
     """LidarFrame.update_object_classes (lidar_frame.py:269-285) for all detections at once.
     class_ids: [C,V] indices into `class_names_sorted` (ALPHABETICAL order = np.unique order); scores [C,V] float32.

@@ -7,6 +7,7 @@ benchmark can call them one by one; `process_frame` chains them.
     ground(points)                 A1-A5   csrc/ground.hip
     to_ref + non-ground gather     B1      csrc/segment.hip (+ torch index plumbing)
     cluster(X)                     B2-B3   csrc/cluster.hip (GPU) + csrc/hdbscan_tree.cpp (host)
+    cluster packing                B3      csrc/hdbscan_tree.cpp (host; default) or csrc/pack.hip (GPU, pack='device')
     ground plane + filters         C1-C2   csrc/segment.hip
     render + encode + score        D1-D9   csrc/render.hip, csrc/vit.hip
     vote                           D10     host numpy (<= ~150 clusters)
@@ -25,7 +26,8 @@ from scipy.spatial.transform import Rotation
 
 from ._lib import (lib, ptr, stream_ptr, check, FilterParams, FILTER_NAMES, FILTER_AND_REQUIRED, FILTER_AND, FILTER_OR, FILTER_NSTATS,
                    FILTER_FLAG_HULL_OVERFLOW)
-from .frame_state import FrameState, pack_clusters, vote, static_from_entropy
+from .frame_state import (FrameState, pack_clusters, vote, static_from_entropy, pack_clusters_device, select_clusters_device,
+                          PACK_MAX_LABEL_BOUND)
 from . import patchworkpp as gpw
 from .hdbscan import HDBSCAN
 from .projection import RealisticProjection, VIEWS_4, VIEWS_6
@@ -103,7 +105,7 @@ class PseudoLabelPipeline:
     def __init__(self, preprocessor_cfg=None, device='cuda:0', vit_dtype='f16', n_views=4, max_points=300_000,
                  clip_model_path='../models/clip/', min_range=1.5, z_offset=1.723, plane_seed=666, clip=None,
                  box_mode='reference', box_workers=4, vit_graph=False, angle_mode='reference', cu_reserve=None, cu_tower=None,
-                 hierarchy=None):
+                 hierarchy=None, pack='host'):
         cfg = preprocessor_cfg if preprocessor_cfg is not None else default_preprocessor_cfg()
         self.cfg = cfg
         self.device = torch.device(device)
@@ -128,6 +130,12 @@ class PseudoLabelPipeline:
         self.cluster_model = HDBSCAN(max_points=self.max_points, device=self.device, **mcfg)
         self.hierarchy = self.cluster_model.hierarchy
         self.prob_threshold = float(_get(ccfg, 'propability_threshold', 0.3))
+        # cluster packing (labels -> ids / packed index lists / offsets) and the valid clusters' sub-lists: 'host' (the labels come down,
+        # csrc/hdbscan_tree.cpp vg_pack_clusters_host groups them, the lists go up again; default) or 'device' (csrc/pack.hip: labels
+        # and lists stay in HBM, one 12-byte read-back sizes the launches that follow) -- the same lists bit for bit
+        # (tests/test_pack_device.py)
+        self.pack = self.parse_pack(pack)
+        self._pack_pinned = None
         self._filters = self._parse_filters(ccfg)
         self.angle_mode = angle_mode             # view direction angle: 'device' | 'reference' (this host's numpy; projection.py)
         self.projection = RealisticProjection(_get(cfg, 'lidar_image_projection'), device=self.device,
@@ -188,6 +196,7 @@ class PseudoLabelPipeline:
         w.clip = self.clip.view()                # shared read-only weights, own workspace
         w._ransac_work = torch.zeros(100 * 36 + 64, dtype=torch.uint8, device=self.device)
         w._xy_pinned = None
+        w._pack_pinned = None
         w._graph_cls = None
         w._ground_stream = None
         w.timings = {}
@@ -374,6 +383,14 @@ class PseudoLabelPipeline:
         return out
 
     @staticmethod
+    def parse_pack(value):
+        """`pack` / device.pack: 'host' or 'device' (None = 'host'); anything else is a ValueError."""
+        value = 'host' if value is None else str(value)
+        if value not in ('host', 'device'):
+            raise ValueError(f"pack: 'host' or 'device', not {value!r}")
+        return value
+
+    @staticmethod
     def _parse_filters(ccfg):
         """clustering.filters / filters_active -> thresholds, the active filters in the order of the config with their combination
         class, and which entry point runs them.  zero_shot_detector.py:279-286: a filter runs when its name is in `filters_active`
@@ -471,7 +488,8 @@ class PseudoLabelPipeline:
 
     # [B2] + [B3]
     def cluster(self, d_X):
-        """d_X: [M,>=3] CUDA float32 (points_ref_wo_ground).  -> labels, probs (host)."""
+        """d_X: [M,>=3] CUDA float32 (points_ref_wo_ground).  -> labels, probs: host arrays, or -- pack='device' with the device
+        hierarchy -- the CUDA tensors the hierarchy stage wrote, handed on as they are (`label` packs them where they lie)."""
         n = d_X.shape[0]
         if n < 2:
             return np.full(n, -1, np.int64), np.zeros(n)
@@ -480,6 +498,8 @@ class PseudoLabelPipeline:
         if self.cluster_model.hierarchy == 'device':
             d_labels, d_probs, _ = self.cluster_model.tree_device(lo, hi, w2, n)
             self._mark('hierarchy_device')
+            if self.pack == 'device':
+                return d_labels, d_probs
             labels, probs = d_labels.cpu().numpy(), d_probs.cpu().numpy()
             self._mark('labels_d2h')
             return labels, probs
@@ -856,6 +876,54 @@ class PseudoLabelPipeline:
         futures = [workers[i % n_workers].thread.submit(run, workers[i % n_workers], i) for i in range(len(prepared))]
         return [f.result() for f in futures]
 
+    def pack_device(self, labels, probs):
+        """Cluster packing on the device (csrc/pack.hip) for labels / probabilities that are CUDA tensors (the device hierarchy's) or host
+        arrays (host hierarchy, the two-frame clusterer: uploaded, 12 bytes per point).  Reads the 12-byte counts back -- the one
+        synchronisation: it sizes every launch that follows -- and queues the lists' copy into pinned host memory.
+        -> (d_index int32 [P], d_seg int32 [C + 1], fetch) with fetch() -> (ids int64 [C], index int32 [P], seg int32 [C + 1]) numpy
+        arrays of the frame's own (it waits for the copy); or None when the frame cannot be packed here (labels beyond int32 or beyond
+        the bound of the call): the caller packs it on the host."""
+        if isinstance(labels, torch.Tensor):
+            d_labels, d_probs = labels, probs
+            n = d_labels.numel()
+            # the hierarchy selects clusters of at least min_cluster_size points: labels 0 .. n / min_cluster_size - 1
+            bound = n // max(self.cluster_model.min_cluster_size, 1) + 1
+        else:
+            labels = np.asarray(labels)
+            n = labels.size
+            hi = int(labels.max()) if n else -1
+            if hi >= PACK_MAX_LABEL_BOUND or (n and int(labels.min()) < np.iinfo(np.int32).min):
+                return None
+            bound = hi + 1
+            d_labels = torch.from_numpy(np.ascontiguousarray(labels, dtype=np.int32)).to(self.device)
+            d_probs = None if probs is None else torch.from_numpy(np.ascontiguousarray(probs, dtype=np.float64)).to(self.device)
+        if n > PACK_MAX_LABEL_BOUND:
+            return None
+        if d_labels.dtype != torch.int32:
+            d_labels = d_labels.to(torch.int32)
+        ids, index, seg, counts = pack_clusters_device(d_labels.contiguous(), None if d_probs is None else d_probs.contiguous(),
+                                                       self.prob_threshold, label_bound=max(bound, 0))
+        C, P, over = (int(v) for v in counts.cpu().numpy())
+        if over:
+            return None
+        # one pinned block per worker: ids (int64) | index | seg (int32), copied out by fetch() before the worker's next frame
+        need = 8 * C + 4 * P + 4 * (C + 1)
+        if self._pack_pinned is None or self._pack_pinned.numel() < need:
+            self._pack_pinned = torch.empty(max(need, 16 * self.max_points + 16), dtype=torch.uint8, pin_memory=True)
+        pin = self._pack_pinned
+        h_ids, h_index, h_seg = pin[:8 * C].view(torch.int64), pin[8 * C:8 * C + 4 * P].view(torch.int32), \
+            pin[8 * C + 4 * P:need].view(torch.int32)
+        h_ids.copy_(ids[:C], non_blocking=True)
+        h_index.copy_(index[:P], non_blocking=True)
+        h_seg.copy_(seg[:C + 1], non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(self.device))
+
+        def fetch():
+            ev.synchronize()
+            return h_ids.numpy().copy(), h_index.numpy().copy(), h_seg.numpy().copy()
+        return index[:P], seg[:C + 1], fetch
+
     def label(self, fs, d_ref, d_X, gidx, labels, probs, entropy=None, t=None, t0=None, tick=None, before_classify=None):
         """Everything after clustering: detections, static flags, filters, classification, boxes, results."""
         t = {} if t is None else t
@@ -864,9 +932,21 @@ class PseudoLabelPipeline:
             t0 = time.perf_counter()
         # per-crop score matrix of THIS frame (empty unless the frame reaches classification): never a previous frame's
         self.last_probs = torch.zeros((0, len(self.class_list)), dtype=torch.float32, device=self.device)
-        ids, index, seg = pack_clusters(labels, probs, self.prob_threshold)
-        fs.set_clusters(ids, index, seg)
-        C = len(ids)
+        packed = self.pack_device(labels, probs) if self.pack == 'device' else None
+        if packed is None:
+            if isinstance(labels, torch.Tensor):         # (device packing refused the frame: a label beyond its bound)
+                labels, probs = labels.cpu().numpy(), None if probs is None else probs.cpu().numpy()
+            ids, index, seg = pack_clusters(labels, probs, self.prob_threshold)
+            d_index = d_seg = None
+        else:
+            d_index, d_seg, fetch = packed
+            if entropy is not None or d_seg.numel() == 1:
+                ids, index, seg = fetch()                # static_from_entropy reads the lists on the host right away
+            else:
+                ids = index = seg = None                 # fetched behind the plane / filter launches
+        C = (d_seg.numel() - 1) if ids is None else len(ids)
+        if ids is not None:
+            fs.set_clusters(ids, index, seg)
         if entropy is not None and C:
             ecfg = _get(_get(self.cfg, 'clustering'), 'entropy_score_filter', None)
             fs.static = static_from_entropy(entropy, index, seg, percentile=float(_get(ecfg, 'percentile', 30) if ecfg else 30),
@@ -875,8 +955,9 @@ class PseudoLabelPipeline:
         if C == 0:
             self.timings = t
             return fs, result
-        d_index = torch.from_numpy(index).to(self.device)
-        d_seg = torch.from_numpy(seg).to(self.device)
+        if d_index is None:
+            d_index = torch.from_numpy(index).to(self.device)
+            d_seg = torch.from_numpy(seg).to(self.device)
         self._mark('pack_clusters+h2d')
         xy_host = xy_ev = None
         if self.box_mode == 'reference':
@@ -884,6 +965,9 @@ class PseudoLabelPipeline:
         plane = self.ground_plane(d_ref, gidx) if self._filters['use_plane'] else np.array([0.0, 0.0, 1.0, 0.0])
         fs.ground_plane_model_ref = plane
         valid, stats = self.filter(d_X, d_index, d_seg, plane, entropy=entropy)
+        if ids is None:
+            ids, index, seg = fetch()                    # pack='device': the lists' copy was queued in front of the plane fit
+            fs.set_clusters(ids, index, seg)
         fs.valid = valid.cpu().numpy().astype(bool)
         if self.last_filter_dict is not None:
             fs.filter_dict = self.last_filter_dict
@@ -896,11 +980,19 @@ class PseudoLabelPipeline:
             self.timings = t
             return fs, result
         # packed sub-list of the valid clusters (classification and boxes are `valid_only`, preprocessing.yaml:81,89)
-        parts = [index[seg[c]:seg[c + 1]] for c in vrows]
-        v_index = np.concatenate(parts)
-        v_seg = np.r_[0, np.cumsum([len(p) for p in parts])].astype(np.int32)
-        d_vindex = torch.from_numpy(v_index).to(self.device)
-        d_vseg = torch.from_numpy(v_seg).to(self.device)
+        if packed is not None:
+            # pack='device': the sub-lists are cut on the device from the filter's own verdict bytes (csrc/pack.hip vg_pack_select); their
+            # sizes follow from the host's copy of the verdict, the host's copy of the lists is built only if host code reads it
+            v_seg = np.r_[0, np.cumsum(seg[vrows + 1] - seg[vrows])].astype(np.int32)
+            d_vindex, d_vseg, _ = select_clusters_device(d_index, d_seg, C, valid, n_index=len(index))
+            d_vindex, d_vseg = d_vindex[:int(v_seg[-1])], d_vseg[:len(vrows) + 1]
+            v_index = None
+        else:
+            parts = [index[seg[c]:seg[c + 1]] for c in vrows]
+            v_index = np.concatenate(parts)
+            v_seg = np.r_[0, np.cumsum([len(p) for p in parts])].astype(np.int32)
+            d_vindex = torch.from_numpy(v_index).to(self.device)
+            d_vseg = torch.from_numpy(v_seg).to(self.device)
         if before_classify is not None:
             before_classify()                    # the frame's clustering / filtering is done, its crops are about to be queued
         self._mark('valid_lists')
@@ -912,6 +1004,8 @@ class PseudoLabelPipeline:
             # queued -- the GPU renders and encodes meanwhile, the helpers have the ViT pass's ~13 ms for their ~2.5 ms (round 5: the
             # request used to sit in front of the render, on the frame's critical path)
             xy_ev.synchronize()
+            if v_index is None:
+                v_index = np.concatenate([index[seg[c]:seg[c + 1]] for c in vrows])        # (the helper processes' request reads it)
             box_fut = self.fit_boxes_async(d_X, v_index, v_seg, d_vindex, d_vseg, xy_host=xy_host, zmin=st[vrows, 1], zmax=st[vrows, 2])
         self._mark('encode+scores')              # (incl. the box request sent while the GPU encodes)
         if box_fut is None:

@@ -176,7 +176,7 @@ class ZeroShotDetector:
                                            z_offset=ga['z_offset'], plane_seed=dev.get('plane_seed', 666), clip=clip_model,
                                            box_mode=dev.get('box_mode', 'reference'), box_workers=dev.get('box_workers', 4),
                                    angle_mode=dev.get('angle_mode', 'reference'), vit_graph=bool(dev.get('vit_graph', False)),
-                                           hierarchy=dev.get('hierarchy', None))
+                                           hierarchy=dev.get('hierarchy', None), pack=dev.get('pack', 'host'))
         self.pipe = pipeline
         if 'needs_entropy' in getattr(pipeline, '_filters', {}):
             PseudoLabelPipeline.check_filter_stages(pipeline._filters, list(cfg.pipeline_active))
@@ -251,7 +251,20 @@ class ZeroShotDetector:
         fs = self.lidar_frame_list[fnr]
         if rows is None:
             index, seg = fs.index, fs.seg_off
-        else:
+        held = self._dev.get(fnr, {}).get('lists')
+        if held is not None and held[0] is fs.index:
+            # device.pack=device: the frame's lists never left the GPU (spatial_clustering); a subset of the clusters is cut there too
+            if rows is None:
+                return held[1], held[2]
+            rows = np.asarray(rows, dtype=np.int64)
+            if len(rows) and np.all(np.diff(rows) > 0):
+                from .frame_state import select_clusters_device
+                mask = np.zeros(fs.n_detections, np.uint8)
+                mask[rows] = 1
+                o_index, o_seg, _ = select_clusters_device(held[1], held[2], fs.n_detections, torch.from_numpy(mask).to(self.pipe.device),
+                                                           n_index=len(fs.index))
+                return o_index[:int((fs.seg_off[rows + 1] - fs.seg_off[rows]).sum())], o_seg[:len(rows) + 1]
+        if rows is not None:
             parts = [fs.cluster_index(c) for c in rows]
             index = np.concatenate(parts) if parts else np.zeros(0, np.int32)
             seg = np.r_[0, np.cumsum([len(p) for p in parts])].astype(np.int32)
@@ -632,7 +645,15 @@ class ZeroShotDetector:
                 labels, probs = TwoFrameClusterer(p.cluster_model, n_frames=n_frames, seed=seed, parts=parts).labels(fnr, X_list, ent_list)
             else:
                 labels, probs = p.cluster(X)
-            fs.set_clusters(*pack_clusters(labels, probs, p.prob_threshold))     # lidar_frame.py:154-248
+            packed = p.pack_device(labels, probs) if getattr(p, 'pack', 'host') == 'device' else None
+            if packed is None:
+                if isinstance(labels, torch.Tensor):
+                    labels, probs = labels.cpu().numpy(), None if probs is None else probs.cpu().numpy()
+                fs.set_clusters(*pack_clusters(labels, probs, p.prob_threshold))     # lidar_frame.py:154-248
+                self._dev[fnr].pop('lists', None)
+            else:
+                fs.set_clusters(*packed[2]())                                        # (the same lists, packed by csrc/pack.hip)
+                self._dev[fnr]['lists'] = (fs.index, packed[0], packed[1])           # read by _cluster_lists while fs.index is this array
             self._box_prefetch.pop(fnr, None)                                    # (requests sent for the frame's previous clusters)
             ent = self._dev[fnr].get('ent')
             if ent is not None and fs.n_detections:
