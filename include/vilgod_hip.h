@@ -308,11 +308,15 @@ int vg_pack_select(const int32_t* d_index, const int32_t* d_seg, int n_clusters,
 /* GPU half of the clustering: exact k-NN core distances and THE minimum spanning tree of the mutual
  * reachability graph under the strict edge order (w2, pair d2, min id, max id) (unique -> identical to the CPU oracle's). */
 typedef struct vg_cluster vg_cluster;
+#define VG_CLUSTER_MAX_K 64 /* largest min_samples of vg_cluster_mst[_nd] */
 int vg_cluster_create(vg_cluster** out, int max_points);
 void vg_cluster_destroy(vg_cluster* h);
 /* d_points [n,stride] f32 (x,y,z first; `points_ref_wo_ground[..., :3]`, zero_shot_detector.py:246).
- * k = min_samples (= min_cluster_size in the reference's configuration; k <= 15): core distance = distance to the
- * k-th nearest OTHER point.  Outputs (device): d_core2 [n] f64 squared core distances in input order (may be NULL);
+ * k = min_samples (= min_cluster_size in the reference's configuration), 1 <= k <= VG_CLUSTER_MAX_K (VG_ERR_ARG outside):
+ * core distance = distance to the k-th nearest OTHER point, +inf for a point with fewer than k others.  k <= 15 keeps each
+ * query's neighbour list in registers; 16 <= k <= 64 keeps it in LDS (per-lane heaps) and, for the queries whose neighbourhood
+ * is wider than their node's shell, in one sorted list across the 64 lanes of a wave -- hence the limit.  Same results
+ * either way: exact, float64.  Outputs (device): d_core2 [n] f64 squared core distances in input order (may be NULL);
  * d_mst_lo/hi [n-1] int32 input indices (lo < hi); d_mst_w2 [n-1] f64 SQUARED weights, ascending.
  * Termination is decided on the device (every kernel of a round returns at once when the tree was complete before the round);
  * the host queues the first six rounds without reading anything back and synchronises `stream` once per batch (one 4-byte

@@ -70,6 +70,9 @@ def _load():
 
 lib = _load()
 
+# largest min_samples vg_cluster_mst[_nd] takes (include/vilgod_hip.h)
+CLUSTER_MAX_K = int(re.search(r'#define\s+VG_CLUSTER_MAX_K\s+(\d+)', open(HEADER).read()).group(1))
+
 
 # vg_cluster_filter_ex: column order of d_verdict / vg_filter_params.active (include/vilgod_hip.h VG_FILTER_*)
 FILTER_NAMES = ('filter_by_number_points', 'filter_by_height', 'filter_by_aspect_ratio', 'filter_by_volume', 'filter_by_area',

@@ -14,7 +14,7 @@ import ctypes
 import numpy as np
 import torch
 
-from ._lib import lib, ptr, stream_ptr, check
+from ._lib import lib, ptr, stream_ptr, check, CLUSTER_MAX_K
 
 
 class HDBSCAN:
@@ -30,8 +30,9 @@ class HDBSCAN:
             raise NotImplementedError('cluster_selection_method=eom, allow_single_cluster=False only')
         self.min_cluster_size = int(min_cluster_size)
         self.min_samples = int(min_samples) if min_samples is not None else self.min_cluster_size
-        if not 1 <= self.min_samples <= 15:
-            raise NotImplementedError('min_samples must be in [1, 15] (register-resident neighbour list)')
+        if not 1 <= self.min_samples <= CLUSTER_MAX_K:
+            raise NotImplementedError(f'min_samples must be in [1, {CLUSTER_MAX_K}] (the neighbour list of an isolated query is one '
+                                      'entry per lane of a wave)')
         self.cluster_selection_epsilon = float(cluster_selection_epsilon)
         self.device = torch.device(device)
         self.max_points = int(max_points)
