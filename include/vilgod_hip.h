@@ -256,6 +256,19 @@ int vg_hdbscan_tree_host(const int32_t* h_lo, const int32_t* h_hi, const double*
                          int min_cluster_size, double eps, int32_t* h_labels, double* h_probs,
                          int32_t* h_n_clusters);
 
+/* vg_hdbscan_tree_host with the library's three cluster-selection options (the semantics of its scikit-learn port,
+ * sklearn/cluster/_hdbscan/_tree.pyx:708-784 selection, :578-641 epsilon, :433-512 labels):
+ *   selection             0 = excess of mass, 1 = leaf (the leaves of the cluster tree; a tree without a split selects nothing)
+ *   allow_single_cluster  0 / 1: the root takes part in excess of mass (birth 0, size = the sum of its child clusters' sizes), the
+ *                         epsilon climb may end at the root, and a selected root holds the points whose own lambda reaches 1 / eps
+ *                         (eps != 0) or the largest lambda among the root's own rows (eps == 0).  A tree of 2 .. min_cluster_size
+ *                         points is all root then (without the option: all noise).
+ *   max_cluster_size      0 = unlimited; excess of mass only: a larger cluster loses to its children whatever the stabilities
+ * Values outside these ranges: VG_ERR_ARG.  (0, 0, 0) is vg_hdbscan_tree_host. */
+int vg_hdbscan_tree_host_ex(const int32_t* h_lo, const int32_t* h_hi, const double* h_w2, int n, int min_cluster_size, double eps,
+                            int selection, int allow_single_cluster, int max_cluster_size, int32_t* h_labels, double* h_probs,
+                            int32_t* h_n_clusters);
+
 /* The same hierarchy stage ON THE DEVICE (csrc/hdbscan_device.hip): d_lo / d_hi / d_w2 = the tree as vg_cluster_mst_nd leaves it
  * (sorted by weight, ties in any order), d_labels [n] / d_probs [n] / d_n_clusters [1] device outputs equal, bit for bit, to what
  * vg_hdbscan_tree_host returns for the same tree.  No host work between the tree and the labels: the stage is a sequence of kernels on
@@ -266,6 +279,12 @@ int vg_hier_create(vg_hier** out, int max_points);
 int vg_hier_destroy(vg_hier* h);
 int vg_hdbscan_tree_device(vg_hier* h, const int32_t* d_lo, const int32_t* d_hi, const double* d_w2, int n, int min_cluster_size,
                            double eps, int32_t* d_labels, double* d_probs, int32_t* d_n_clusters, void* stream);
+/* ... with selection / allow_single_cluster / max_cluster_size as vg_hdbscan_tree_host_ex takes them (VG_ERR_ARG outside their ranges):
+ * bit for bit what vg_hdbscan_tree_host_ex returns, by the same sequence of kernels (the root's chain statistics are computed only
+ * with allow_single_cluster).  (0, 0, 0) is vg_hdbscan_tree_device. */
+int vg_hdbscan_tree_device_ex(vg_hier* h, const int32_t* d_lo, const int32_t* d_hi, const double* d_w2, int n, int min_cluster_size,
+                              double eps, int selection, int allow_single_cluster, int max_cluster_size, int32_t* d_labels,
+                              double* d_probs, int32_t* d_n_clusters, void* stream);
 
 /* LidarFrame.generate_detections' grouping (src/vilgod/lidar_frame.py:163-167, 230-237; Detection objects :42-58 of
  * src/dataclass/objects.py) on the host: points whose membership probability is < threshold become noise (h_probs may be NULL),

@@ -2,8 +2,11 @@
 the device stage (csrc/hdbscan_device.hip + copy of labels and probabilities to the host), same tree, results compared bit for bit.
 
     python tools/bench_hierarchy.py [--points 150000] [--frames 4] [--reps 20]
+    python tools/bench_hierarchy.py --selection leaf | --allow-single-cluster | --max-cluster-size 2000     # the library's selection options
+    python tools/bench_hierarchy.py --json out.json        # one JSON line per frame appended: medians with the rounds' min and max
 """
 import argparse
+import json
 import os
 import sys
 import time
@@ -22,10 +25,18 @@ def main():
     ap.add_argument('--points', type=int, default=150_000)
     ap.add_argument('--frames', type=int, default=4)
     ap.add_argument('--reps', type=int, default=20)
+    ap.add_argument('--selection', choices=('eom', 'leaf'), default='eom', help='cluster_selection_method')
+    ap.add_argument('--allow-single-cluster', action='store_true')
+    ap.add_argument('--max-cluster-size', type=int, default=0, help='0: unlimited')
+    ap.add_argument('--json', default=None, help='append one JSON line per frame to this file')
+    ap.add_argument('--tag', default='', help='copied into the JSON lines')
     args = ap.parse_args()
     dev = torch.device('cuda:0')
     pipe = PseudoLabelPipeline(device=dev, max_points=args.points + 10_000, clip_model_path='/nonexistent')
-    model = pipe.cluster_model
+    mcfg = dict(pipe._mcfg, cluster_selection_method=args.selection, allow_single_cluster=args.allow_single_cluster,
+                max_cluster_size=args.max_cluster_size)
+    model = HDBSCAN(max_points=args.points + 10_000, device=dev, **mcfg)
+    sel = model.selection_args
     hier = DeviceHierarchy(max_points=args.points + 10_000, device=dev)
     mcs, eps = model.min_cluster_size, model.cluster_selection_epsilon
     for f in range(args.frames):
@@ -44,7 +55,7 @@ def main():
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             t0 = time.perf_counter()
             e0.record()
-            dl, dp, dn = hier.tree_async(lo, hi, w2, n, mcs, eps)
+            dl, dp, dn = hier.tree_async(lo, hi, w2, n, mcs, eps, None, *sel)
             e1.record()
             L1, P1 = dl.cpu().numpy(), dp.cpu().numpy()
             dev_ms.append((time.perf_counter() - t0) * 1e3)
@@ -61,6 +72,13 @@ def main():
             extra = f'  splits {ns_.value}  sweeps over the cluster tree {sw_.value}'
         same = int(dn.item()) == c0 and np.array_equal(L0, L1) and np.array_equal(P0.view(np.uint64), P1.view(np.uint64))
         med = lambda a: float(np.median(a))
+        if args.json:
+            span = lambda a: dict(median=round(med(a), 4), min=round(float(np.min(a)), 4), max=round(float(np.max(a)), 4))
+            with open(args.json, 'a') as fh:
+                fh.write(json.dumps(dict(tag=args.tag, frame=f, n=int(n), clusters=int(c0), reps=args.reps, selection=args.selection,
+                                         allow_single_cluster=bool(args.allow_single_cluster), max_cluster_size=args.max_cluster_size,
+                                         host_stage_ms=span(host_ms), device_stage_ms=span(dev_ms), device_kernels_ms=span(dev_kernel_ms),
+                                         bit_identical=bool(same))) + '\n')
         print(f'frame {f}: n {n}  clusters {c0}  host stage (D2H of the tree + hdbscan_tree.cpp) {med(host_ms):.2f} ms   device stage + D2H of labels '
               f'{med(dev_ms):.2f} ms (kernels {med(dev_kernel_ms):.2f} ms)   results {"bit-identical" if same else "DIFFERENT"}{extra}', flush=True)
 

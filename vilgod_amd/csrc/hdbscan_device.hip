@@ -16,9 +16,11 @@
 //   scan + k_hd_scatter                the split edges, a few hundred, in rank order
 //   k_hd_tree_a                        ONE lane, union-find in LDS: Kruskal over the splits on the segments = the cluster tree
 //   k_hd_chain + radix sort            every chain node's cluster (a walk up the cluster tree); the chains grouped by cluster  (R4)
-//   k_hd_chain_stats                   a wave per cluster: its chain by descending rank, summed in the library's order     (R6)
+//   k_hd_chain_stats                   a wave per cluster: its chain by descending rank, summed in the library's order     (R6);
+//                                      with allow_single_cluster one more wave over the ROOT's chain
 //   k_hd_tree_bc                       ONE workgroup: cluster sizes, the stabilities' last rows, excess of mass; dendrogram depths and
-//                                      the library's BFS numbering (R5); epsilon; flat labels
+//                                      the library's BFS numbering (R5); the selection (excess of mass with max_cluster_size and, under
+//                                      allow_single_cluster, the root; or the leaves); epsilon; flat labels
 // The cluster tree's arrays (a few hundred splits) are staged in LDS by every kernel that sweeps or walks the tree (HdCarve).
 //   k_hd_points                        label and probability of every point
 // The one-workgroup kernel sweeps the cluster tree level by level (as many sweeps, one barrier each, as it is high).  float64 throughout; compiled with
@@ -167,7 +169,7 @@ __device__ __forceinline__ void hd_chain_body(const HdView& v, const HdView& w, 
     if (r < v.m) {
         const HdChainRec rec = hd_chain_rec(v, r, c);
         v.crec[r] = rec;
-        ckey[r] = hd_chain_sortkey(rec); crank[r] = (unsigned)r;
+        ckey[r] = hd_chain_sortkey_root(rec); crank[r] = (unsigned)r;
     }
     // of the root (the points no cluster holds: most chain nodes) only the chain length is read: one atomic per wave
     const unsigned long long roots = __ballot(c == 0);
@@ -188,11 +190,9 @@ __global__ __launch_bounds__(HD_NT) void k_hd_chain(HdView v, unsigned* __restri
 
 // a wave per cluster over its run of the sorted chain nodes: chain length, points, largest lambda, and the rows of its own chain summed
 // in the library's order (descending rank)
-__global__ __launch_bounds__(HD_NT) void k_hd_chain_stats(HdView v) {
-    const int ns = *v.ns, ncl = 2 * ns + 1;
-    const int lane = threadIdx.x & 63, nw = gridDim.x * (HD_NT / 64);
-    for (int c = 1 + (int)((blockIdx.x * HD_NT + threadIdx.x) >> 6); c < ncl; c += nw) {
-        const int b = hd_lower_bound_u32(v.chain_key, v.m, (unsigned)c), e = hd_lower_bound_u32(v.chain_key, v.m, (unsigned)c + 1u);
+__device__ __forceinline__ void hd_chain_stats_wave(const HdView& v, int c, int lane) {
+    {
+        const int b = hd_lower_bound_u32(v.chain_key, v.m, hd_chain_key_of(c)), e = hd_lower_bound_u32(v.chain_key, v.m, hd_chain_key_of(c) + 1u);
         const double birth = hd_birth(v, c);
         double s = 0.0;
         int np = 0;
@@ -233,6 +233,14 @@ __global__ __launch_bounds__(HD_NT) void k_hd_chain_stats(HdView v) {
         }
     }
 }
+// allow_single_cluster: the ROOT's chain too (the points no cluster holds: most of a LiDAR frame's chain nodes, one wave's strictly ordered
+// additions over all of them) -- by the grid's last wave, which has no cluster of its own unless the tree has thousands of them
+__global__ __launch_bounds__(HD_NT) void k_hd_chain_stats(HdView v) {
+    const int ns = *v.ns, ncl = 2 * ns + 1;
+    const int lane = threadIdx.x & 63, nw = gridDim.x * (HD_NT / 64), w = (int)((blockIdx.x * HD_NT + threadIdx.x) >> 6);
+    for (int c = 1 + w; c < ncl; c += nw) hd_chain_stats_wave(v, c, lane);
+    if (v.allow_single && w == nw - 1) hd_chain_stats_wave(v, 0, lane);
+}
 
 // ONE workgroup over the cluster tree, its arrays in LDS: bottom-up (sizes, the stabilities' last rows, excess of mass), top-down (dendrogram
 // depths, preorder), the library's BFS numbering, the selection, cluster_selection_epsilon, flat labels.  A sweep = one barrier.
@@ -254,6 +262,10 @@ __device__ __forceinline__ void hd_tree_bc_body(const HdView& v, unsigned long l
     const int t = threadIdx.x, T = blockDim.x, ncl = 2 * ns + 1;
     HD_STAMP(5)
     HD_SWEEPS(hd_up_all(v, i, sweep))
+    if (v.allow_single) {                                          // (before stab2 turns into the BFS keys)
+        if (t == 0) hd_root_node(v, ns);
+        __syncthreads();
+    }
     HD_STAMP(6)
     HD_SWEEPS(hd_down_order(v, i, sweep))
     HD_STAMP(7)
@@ -278,14 +290,14 @@ __device__ __forceinline__ void hd_tree_bc_body(const HdView& v, unsigned long l
     for (int i = t; i < ns; i += T) v.q[(int)(bfs_key[i] & ((1u << HD_RANK_BITS) - 1u))] = i;
     __syncthreads();
     HD_STAMP(8)
-    for (int c = 1 + t; c < ncl; c += T) hd_select_eom(v, c);
+    for (int c = t; c < ncl; c += T) hd_select(v, c);
     __syncthreads();
     HD_STAMP(9)
     const bool use_eps = v.eps != 0.0 && ncl > 1;
     if (use_eps) {
-        for (int c = 1 + t; c < ncl; c += T) hd_eps_candidates(v, c);
+        for (int c = t; c < ncl; c += T) hd_eps_candidates(v, c);
         __syncthreads();
-        for (int c = 1 + t; c < ncl; c += T) hd_eps_select(v, c);
+        for (int c = t; c < ncl; c += T) hd_eps_select(v, c);
         __syncthreads();
     }
     HD_STAMP(10)
@@ -352,6 +364,17 @@ __global__ __launch_bounds__(HD_NT) void k_hd_noise(int n, int* __restrict__ lab
     const int p = blockIdx.x * HD_NT + threadIdx.x;
     if (p < n) { labels[p] = -1; probs[p] = 0.0; }
     if (p == 0 && ncl) *ncl = 0;
+}
+// allow_single_cluster with the excess of mass on a tree of 2 .. min_cluster_size points: every point is a row of the root at the lambda of
+// the heaviest edge, the root is the one cluster (hdbscan_tree.cpp on the same tree: label 0 iff that lambda reaches 1 / eps; probability
+// lambda / lambda)
+__global__ __launch_bounds__(HD_NT) void k_hd_single(int n, const double* __restrict__ w2, double eps, int* __restrict__ labels, double* __restrict__ probs,
+                                                     int* __restrict__ ncl) {
+    const int p = blockIdx.x * HD_NT + threadIdx.x;
+    const double lam = hd_lambda(w2[n - 2]);
+    const bool in = lam >= (eps != 0.0 ? 1.0 / eps : lam);
+    if (p < n) { labels[p] = in ? 0 : -1; probs[p] = in ? 1.0 : 0.0; }
+    if (p == 0 && ncl) *ncl = 1;
 }
 
 template <typename T>
@@ -434,9 +457,22 @@ int vg_hier_destroy(vg_hier* h) {
 
 int vg_hdbscan_tree_device(vg_hier* h, const int32_t* d_lo, const int32_t* d_hi, const double* d_w2, int n, int min_cluster_size, double eps,
                            int32_t* d_labels, double* d_probs, int32_t* d_n_clusters, void* stream) {
+    return vg_hdbscan_tree_device_ex(h, d_lo, d_hi, d_w2, n, min_cluster_size, eps, 0, 0, 0, d_labels, d_probs, d_n_clusters, stream);
+}
+
+int vg_hdbscan_tree_device_ex(vg_hier* h, const int32_t* d_lo, const int32_t* d_hi, const double* d_w2, int n, int min_cluster_size, double eps,
+                              int selection, int allow_single_cluster, int max_cluster_size, int32_t* d_labels, double* d_probs,
+                              int32_t* d_n_clusters, void* stream) {
     if (!h || n < 0 || !d_labels || !d_probs || min_cluster_size < 2 || min_cluster_size > HD_MAX_MCS) return VG_ERR_ARG;
+    if (selection < 0 || selection > 1 || allow_single_cluster < 0 || allow_single_cluster > 1 || max_cluster_size < 0) return VG_ERR_ARG;
     if (n > h->max_points) return VG_ERR_CAPACITY;
     hipStream_t st = (hipStream_t)stream;
+    if (n <= min_cluster_size && n >= 2 && allow_single_cluster && selection == 0) {
+        if (!d_w2) return VG_ERR_ARG;
+        hipLaunchKernelGGL(k_hd_single, dim3(vg_div_up(n, HD_NT)), dim3(HD_NT), 0, st, n, d_w2, eps, d_labels, d_probs, d_n_clusters);
+        VG_LAUNCH_CHECK();
+        return VG_OK;
+    }
     if (n <= min_cluster_size) {
         if (n > 0 || d_n_clusters) hipLaunchKernelGGL(k_hd_noise, dim3(vg_div_up(std::max(n, 1), HD_NT)), dim3(HD_NT), 0, st, n, d_labels, d_probs, d_n_clusters);
         VG_LAUNCH_CHECK();
@@ -446,6 +482,7 @@ int vg_hdbscan_tree_device(vg_hier* h, const int32_t* d_lo, const int32_t* d_hi,
     const int m = n - 1;
     HdView v = h->v;
     v.n = n; v.m = m; v.mcs = min_cluster_size; v.ncap = n / min_cluster_size + 2; v.eps = eps;
+    v.leaf = selection; v.allow_single = allow_single_cluster; v.max_size = max_cluster_size;
     v.lo = h->lo; v.hi = h->hi; v.w2 = h->w2; v.adj_off = h->adj_off; v.adj = h->adj;
     v.labels = d_labels; v.probs = d_probs;
     const dim3 B(HD_NT);

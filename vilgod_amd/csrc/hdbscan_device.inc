@@ -110,6 +110,10 @@ struct HdView {
     int* n_clusters;                 // [1]
     int* labels;                     // [n]
     double* probs;                   // [n]
+    // the library's cluster-selection options (zero: excess of mass, the root never selected, no size limit)
+    int leaf;                        // cluster_selection_method = 'leaf'
+    int allow_single;                // allow_single_cluster
+    int max_size;                    // max_cluster_size; 0: unlimited
 };
 
 // The strict (w2, lo, hi) order from the weight order: edge i of the weight-sorted input moves, inside its run of equal weights, to the
@@ -273,6 +277,11 @@ HD_FN HdChainRec hd_chain_rec(const HdView& v, int r, int c) {
 #define HD_CHAIN_PAD 0x3FFFFFu
 #define HD_CHAIN_KEY_BITS 22
 HD_FN unsigned hd_chain_sortkey(const HdChainRec& rec) { return rec.c > 0 ? (unsigned)rec.c : HD_CHAIN_PAD; }
+// ... with the root's chain as a run of its own between the clusters' and the other edges (allow_single_cluster reads all of it: the
+// root's stability and largest lambda); every other run is where hd_chain_sortkey puts it
+#define HD_CHAIN_ROOT 0x3FFFFEu
+HD_FN unsigned hd_chain_sortkey_root(const HdChainRec& rec) { return rec.c > 0 ? (unsigned)rec.c : (rec.c == 0 ? HD_CHAIN_ROOT : HD_CHAIN_PAD); }
+HD_FN unsigned hd_chain_key_of(int c) { return c > 0 ? (unsigned)c : HD_CHAIN_ROOT; }
 
 HD_FN int hd_lower_bound_u32(const unsigned* a, int n, unsigned key) {
     int lo = 0, hi = n;
@@ -288,7 +297,7 @@ HD_FN double hd_stab_terms(double s, double t, int kc) {
 }
 // phase c in [1, 2 ns + 1) -- reference form (the emulation; the kernel's wave form is k_hd_chain_stats)
 HD_FN void hd_chain_stats(const HdView& v, int c) {
-    const int b = hd_lower_bound_u32(v.chain_key, v.m, (unsigned)c), e = hd_lower_bound_u32(v.chain_key, v.m, (unsigned)c + 1u);
+    const int b = hd_lower_bound_u32(v.chain_key, v.m, hd_chain_key_of(c)), e = hd_lower_bound_u32(v.chain_key, v.m, hd_chain_key_of(c) + 1u);
     const double birth = hd_birth(v, c);
     double s = 0.0;
     int np = 0;
@@ -300,6 +309,9 @@ HD_FN void hd_chain_stats(const HdView& v, int c) {
     v.chainlen[c] = e - b; v.npts[c] = np; v.stab[c] = s;
     v.death[c] = e > b ? v.crec[v.chain_rank[b]].lam : 0.0;       // the lowest rank: the largest lambda
 }
+// allow_single_cluster: the same of the ROOT's chain (c = 0, birth 0; the chains sorted by hd_chain_sortkey_root) -- the longest chain of
+// a LiDAR frame, walked only when the option asks for the root's stability
+HD_FN void hd_chain_stats_root(const HdView& v) { hd_chain_stats(v, 0); }
 
 // ---- R5 / R6: the cluster tree, relaxation phases over the splits k in [0, ns) -----------------------------------------------------
 // A relaxation phase returns 1 when it computed its element; the caller repeats the phase, `sweep` = 0, 1, 2, ..., until no element
@@ -341,8 +353,10 @@ HD_FN void hd_up_node(const HdView& v, int k, int sweep) {         // (both kids
     v.csize[cl] = cs_l; v.csize[cr] = cs_r;
     v.stab[cl] = s_l; v.stab[cr] = s_r;
     v.death[cl] = d_l; v.death[cr] = d_r;
-    if (sub_l > s_l) { v.wins[cl] = 0; v.stab2[cl] = sub_l; } else { v.wins[cl] = 1; v.stab2[cl] = s_l; }
-    if (sub_r > s_r) { v.wins[cr] = 0; v.stab2[cr] = sub_r; } else { v.wins[cr] = 1; v.stab2[cr] = s_r; }
+    // (max_cluster_size: a larger cluster loses to its children whatever the stabilities, and takes their stability)
+    const int mx = v.max_size;
+    if (sub_l > s_l || (mx > 0 && cs_l > mx)) { v.wins[cl] = 0; v.stab2[cl] = sub_l; } else { v.wins[cl] = 1; v.stab2[cl] = s_l; }
+    if (sub_r > s_r || (mx > 0 && cs_r > mx)) { v.wins[cr] = 0; v.stab2[cr] = sub_r; } else { v.wins[cr] = 1; v.stab2[cr] = s_r; }
     v.tot[k] = cs_l + cs_r;
     v.nsub[k] = 1 + ns_l + ns_r;
     hd_store_i32(&v.done[k], sweep + 1);
@@ -365,6 +379,26 @@ HD_FN int hd_up_all(const HdView& v, int k, int sweep) {
         x = p;
     }
     return 1;
+}
+// allow_single_cluster, ONE element behind the bottom-up sweeps (ns: the number of splits): the root as a cluster of the excess of mass --
+// its stability's last two rows (the root split's children; birth 0), its largest lambda, its size = the two child clusters' (the
+// library counts no point that leaves the root itself; a tree without a split: 0)
+HD_FN void hd_root_node(const HdView& v, int ns) {
+    double s = v.stab[0], sub = 0.0, d = v.death[0];
+    int sz = 0;
+    if (ns > 0) {
+        const int k = ns - 1;                                      // the root split: the one of the highest rank
+        const double lam = v.lam_split[k];
+        const int a0 = v.csize[1 + 2 * k], a1 = v.csize[2 + 2 * k];
+        s += (lam - 0.0) * (double)a0;
+        s += (lam - 0.0) * (double)a1;
+        if (lam > d) d = lam;
+        sub += v.stab2[1 + 2 * k];
+        sub += v.stab2[2 + 2 * k];
+        sz = a0 + a1;
+    }
+    v.csize[0] = sz; v.stab[0] = s; v.death[0] = d;
+    v.wins[0] = (sub > s || (v.max_size > 0 && sz > v.max_size)) ? 0 : 1;
 }
 // top-down: dendrogram depth of the split node and its preorder index in the split tree (R5)
 HD_FN void hd_down_node(const HdView& v, int k, int sweep) {       // (the parent is complete)
@@ -401,22 +435,32 @@ HD_FN bool hd_bfs_before(int da, int pa, int db, int pb) { return da < db || (da
 HD_FN int hd_final_id(const HdView& v, int c) { return c == 0 ? 0 : 2 * v.q[(c - 1) >> 1] + 1 + ((c - 1) & 1); }
 HD_FN int hd_cluster_parent(const HdView& v, int c) { return hd_cluster_above(v, (c - 1) >> 1); }       // c >= 1
 
-// phase c in [1, 2 ns + 1): a cluster stays selected iff it wins and no cluster above it (the root aside) does
+// phase c in [1, 2 ns + 1): a cluster stays selected iff it wins and no cluster above it does (the root: only with allow_single_cluster)
 HD_FN void hd_select_eom(const HdView& v, int c) {
     bool sel = v.wins[c];
     for (int a = hd_cluster_parent(v, c); sel && a > 0; a = hd_cluster_parent(v, a)) if (v.wins[a]) sel = false;
+    if (sel && v.allow_single && v.wins[0]) sel = false;
     v.selected[c] = sel;
     v.cand[c] = 0;
 }
+// phase c in [0, 2 ns + 1): the selection by the options -- the root (selected only by the excess of mass with allow_single_cluster);
+// 'leaf': cluster 1 + 2 k + side is a leaf of the cluster tree iff no split hangs below (k, side) -- a tree without a split has no leaf and
+// selects nothing, allow_single_cluster or not, like the library; else the excess of mass
+HD_FN void hd_select(const HdView& v, int c) {
+    if (c == 0) { v.selected[0] = (v.allow_single && !v.leaf) ? v.wins[0] : 0; v.cand[0] = 0; return; }
+    if (v.leaf) { v.selected[c] = v.kid[c - 1] < 0 ? 1 : 0; v.cand[c] = 0; return; }
+    hd_select_eom(v, c);
+}
 // cluster_selection_epsilon, phase c in [1, 2 ns + 1) (hdbscan_tree.cpp: a selected cluster born below eps climbs to the first ancestor
-// born above it, or stops under the root)
+// born above it, or stops under the root -- AT the root with allow_single_cluster).  With allow_single_cluster the phases run from c = 0:
+// a selected root (birth 0: 1 / birth = inf) is its own candidate, which is the library's "only the root is selected" shortcut.
 HD_FN void hd_eps_candidates(const HdView& v, int c) {
     if (!v.selected[c]) return;
     if (1.0 / hd_birth(v, c) < v.eps) {
         int node = c;
         while (true) {
             const int p = hd_cluster_parent(v, node);
-            if (p == 0) break;
+            if (p == 0) { if (v.allow_single) node = 0; break; }
             if (1.0 / hd_birth(v, p) > v.eps) { node = p; break; }
             node = p;
         }
@@ -426,19 +470,23 @@ HD_FN void hd_eps_candidates(const HdView& v, int c) {
 }
 HD_FN void hd_eps_select(const HdView& v, int c) {                 // phase c in [1, 2 ns + 1), after a barrier behind hd_eps_candidates
     bool sel = v.cand[c];
-    for (int a = hd_cluster_parent(v, c); sel && a > 0; a = hd_cluster_parent(v, a)) if (v.cand[a]) sel = false;
+    for (int a = c > 0 ? hd_cluster_parent(v, c) : 0; sel && a > 0; a = hd_cluster_parent(v, a)) if (v.cand[a]) sel = false;
+    if (sel && c > 0 && v.allow_single && v.cand[0]) sel = false;
     v.wins[c] = sel;                                               // (wins is free now: the new selection, read by the next phase)
 }
 // phase c in [0, 2 ns + 1): sel_by_final[final id] = selected (then an exclusive scan over 2 ns + 1 entries gives the flat labels)
 HD_FN void hd_selected_by_final(const HdView& v, int c, bool use_eps) {
-    const bool sel = c == 0 ? false : (use_eps ? v.wins[c] : v.selected[c]);
+    const bool sel = (c == 0 && !v.allow_single) ? false : (use_eps ? v.wins[c] : v.selected[c]);
     v.selected[c] = sel;
     v.sel_by_final[hd_final_id(v, c)] = sel ? 1 : 0;
 }
-// phase c in [0, 2 ns + 1), sel_by_final scanned (exclusive): the nearest selected cluster at or above c owns c's points
+// phase c in [0, 2 ns + 1), sel_by_final scanned (exclusive): the nearest selected cluster at or above c owns c's points.  A selected root
+// (allow_single_cluster; then it is the one cluster, label 0) owns them under a threshold on the point's own lambda: out_label = HD_ROOT_OWNED.
+#define HD_ROOT_OWNED (-2)
 HD_FN void hd_owner(const HdView& v, int c) {
     int o = c;
     while (o > 0 && !v.selected[o]) o = hd_cluster_parent(v, o);
+    if (o == 0 && v.allow_single && v.selected[0]) { v.out_label[c] = HD_ROOT_OWNED; v.out_death[c] = v.death[0]; return; }
     if (o <= 0) { v.out_label[c] = -1; v.out_death[c] = 0.0; return; }
     v.out_label[c] = v.sel_by_final[hd_final_id(v, o)];
     v.out_death[c] = v.death[o];
@@ -446,8 +494,12 @@ HD_FN void hd_owner(const HdView& v, int c) {
 // phase p in [0, n)
 HD_FN void hd_point(const HdView& v, int p) {
     const HdChainRec rec = v.crec[v.a[p]];
-    const int lab = v.out_label[rec.c];
-    if (lab < 0) { v.labels[p] = -1; v.probs[p] = 0.0; return; }
+    int lab = v.out_label[rec.c];
+    if (lab < 0) {
+        // the root as the one cluster: the point's own lambda against 1 / eps, or without eps the largest lambda among the root's own rows
+        if (lab != HD_ROOT_OWNED || !(rec.lam >= (v.eps != 0.0 ? 1.0 / v.eps : v.out_death[rec.c]))) { v.labels[p] = -1; v.probs[p] = 0.0; return; }
+        lab = 0;
+    }
     const double mx = v.out_death[rec.c], lam = rec.lam;
     v.labels[p] = lab;
     v.probs[p] = (mx == 0.0 || isinf(lam)) ? 1.0 : (lam < mx ? lam : mx) / mx;

@@ -11,7 +11,8 @@
 //   single linkage  sklearn/cluster/_hdbscan/_linkage.pyx:226-274
 //   condense        _tree.pyx:122-238      stability :240-278      EOM :729-741
 //   epsilon         :578-641, :743-761     labels    :433-512      probabilities :515-554
-// allow_single_cluster = False, cluster_selection_method = 'eom' (library defaults).
+// The library's defaults are allow_single_cluster = False, cluster_selection_method = 'eom', max_cluster_size = None; the _ex entry
+// takes the three as arguments (_tree.pyx:708-784 selection, :589-591 the climb to the root, :497-508 the root's labels).
 #include <math.h>
 #include <stdint.h>
 #include <algorithm>
@@ -41,16 +42,19 @@ struct Work {
 
 }  // namespace
 
-extern "C" int vg_hdbscan_tree_host(const int32_t* h_lo, const int32_t* h_hi, const double* h_w2, int n,
-                                    int min_cluster_size, double eps, int32_t* h_labels, double* h_probs,
-                                    int32_t* h_n_clusters) {
+extern "C" int vg_hdbscan_tree_host_ex(const int32_t* h_lo, const int32_t* h_hi, const double* h_w2, int n,
+                                       int min_cluster_size, double eps, int selection, int allow_single_cluster,
+                                       int max_cluster_size, int32_t* h_labels, double* h_probs, int32_t* h_n_clusters) {
     if (n < 0 || (n > 1 && (!h_lo || !h_hi || !h_w2)) || !h_labels || !h_probs || min_cluster_size < 2) return 1;
+    if (selection < 0 || selection > 1 || allow_single_cluster < 0 || allow_single_cluster > 1 || max_cluster_size < 0) return 1;
+    const bool leaf = selection == 1, single = allow_single_cluster != 0;
     if (h_n_clusters) *h_n_clusters = 0;
     for (int i = 0; i < n; ++i) {
         h_labels[i] = -1;
         h_probs[i] = 0.0;
     }
-    if (n <= min_cluster_size) return 0;
+    // (a tree too small for a split inside the root still has a root: with allow_single_cluster its points are the root's rows)
+    if (n <= min_cluster_size && !(single && !leaf && n >= 2)) return 0;
     const int m = n - 1;
     // ---- strict total order (w2, lo, hi): the GPU sorts by weight only, fix up runs of equal weight ----
     static thread_local Work ws;
@@ -193,28 +197,38 @@ extern "C" int vg_hdbscan_tree_host(const int32_t* h_lo, const int32_t* h_hi, co
         std::vector<int> cur(kid_off.begin(), kid_off.end() - 1);
         for (int c = 1; c < nc; ++c) kids[cur[cpar[c]]++] = c;
     }
-    // ---- excess of mass ----------------------------------------------------------------------------
+    // ---- selection: excess of mass (the root takes part with allow_single_cluster: birth 0, size = its child clusters', _tree.pyx:724-727;
+    // a cluster above max_cluster_size loses to its children whatever the stabilities, :735), or the leaves of the cluster tree ---------
     std::vector<char> selected(nc, 1);
-    selected[0] = 0;
-    for (int c = nc - 1; c >= 1; --c) {
-        double sub = 0.0;
-        for (int k = kid_off[c]; k < kid_off[c + 1]; ++k) sub += stab[kids[k]];
-        if (sub > stab[c]) {
-            selected[c] = 0;
-            stab[c] = sub;
-        } else {
-            stack.clear();
-            for (int k = kid_off[c]; k < kid_off[c + 1]; ++k) stack.push_back(kids[k]);
-            while (!stack.empty()) {
-                int k = stack.back();
-                stack.pop_back();
-                selected[k] = 0;
-                for (int j = kid_off[k]; j < kid_off[k + 1]; ++j) stack.push_back(kids[j]);
+    selected[0] = single ? 1 : 0;
+    if (leaf) {
+        for (int c = 0; c < nc; ++c) selected[c] = c > 0 && kid_off[c] == kid_off[c + 1];     // (no leaf at all: nothing, :763-784)
+    } else {
+        std::vector<int> csz(nc, 0);
+        for (size_t i = 0; i < nrows; ++i)
+            if (r_size[i] > 1) csz[r_child[i]] = r_size[i];
+        for (int k = kid_off[0]; k < kid_off[1]; ++k) csz[0] += csz[kids[k]];
+        for (int c = nc - 1; c >= (single ? 0 : 1); --c) {
+            double sub = 0.0;
+            for (int k = kid_off[c]; k < kid_off[c + 1]; ++k) sub += stab[kids[k]];
+            if (sub > stab[c] || (max_cluster_size > 0 && csz[c] > max_cluster_size)) {
+                selected[c] = 0;
+                stab[c] = sub;
+            } else {
+                stack.clear();
+                for (int k = kid_off[c]; k < kid_off[c + 1]; ++k) stack.push_back(kids[k]);
+                while (!stack.empty()) {
+                    int k = stack.back();
+                    stack.pop_back();
+                    selected[k] = 0;
+                    for (int j = kid_off[k]; j < kid_off[k + 1]; ++j) stack.push_back(kids[j]);
+                }
             }
         }
     }
     // ---- cluster_selection_epsilon -------------------------------------------------------------------
-    if (eps != 0.0 && nc > 1) {
+    // (a selected root is alone and skips the search, :747-749; with allow_single_cluster the climb may end AT the root, :589-591)
+    if (eps != 0.0 && nc > 1 && !selected[0]) {
         std::vector<char> cand(nc, 0);
         for (int c = 1; c < nc; ++c) {
             if (!selected[c]) continue;
@@ -222,7 +236,10 @@ extern "C" int vg_hdbscan_tree_host(const int32_t* h_lo, const int32_t* h_hi, co
                 int node = c;
                 while (true) {
                     int p = cpar[node];
-                    if (p == 0) break;
+                    if (p == 0) {
+                        if (single) node = 0;
+                        break;
+                    }
                     if (1.0 / birth[p] > eps) { node = p; break; }
                     node = p;
                 }
@@ -237,19 +254,25 @@ extern "C" int vg_hdbscan_tree_host(const int32_t* h_lo, const int32_t* h_hi, co
             bool nested = false;
             for (int a = cpar[c]; a > 0; a = cpar[a])
                 if (cand[a]) { nested = true; break; }
-            selected[c] = !nested;
+            selected[c] = !nested && !cand[0];
         }
+        selected[0] = cand[0];
     }
     // ---- labels + probabilities -------------------------------------------------------------------------
     std::vector<int> label_of(nc, -1), owner(nc, -1);
     int nl = 0;
-    for (int c = 1; c < nc; ++c)
+    for (int c = 0; c < nc; ++c)
         if (selected[c]) label_of[c] = nl++;
+    if (selected[0]) owner[0] = 0;
     for (int c = 1; c < nc; ++c) owner[c] = selected[c] ? c : owner[cpar[c]];
+    // the root as the one selected cluster holds a point iff the point's own lambda reaches 1 / eps, or, without eps, the largest lambda
+    // among the root's own rows (_tree.pyx:497-508)
+    const double root_threshold = eps != 0.0 ? 1.0 / eps : death[0];
     for (size_t i = 0; i < nrows; ++i) {
         if (r_size[i] != 1) continue;
         const int o = owner[r_parent[i]];
         if (o < 0) continue;
+        if (o == 0 && !(r_lambda[i] >= root_threshold)) continue;
         const int pt = r_child[i];
         h_labels[pt] = label_of[o];
         const double mx = death[o], lam = r_lambda[i];
@@ -257,6 +280,12 @@ extern "C" int vg_hdbscan_tree_host(const int32_t* h_lo, const int32_t* h_hi, co
     }
     if (h_n_clusters) *h_n_clusters = nl;
     return 0;
+}
+
+extern "C" int vg_hdbscan_tree_host(const int32_t* h_lo, const int32_t* h_hi, const double* h_w2, int n,
+                                    int min_cluster_size, double eps, int32_t* h_labels, double* h_probs,
+                                    int32_t* h_n_clusters) {
+    return vg_hdbscan_tree_host_ex(h_lo, h_hi, h_w2, n, min_cluster_size, eps, 0, 0, 0, h_labels, h_probs, h_n_clusters);
 }
 
 // LidarFrame.generate_detections' grouping (src/vilgod/lidar_frame.py:163-167, 230-237) as one counting sort: labels of points whose

@@ -4,8 +4,12 @@ min_cluster_size=15, metric='euclidean', core_dist_n_jobs=-1)`; `.fit(X)` then `
 `.probabilities_`, src/vilgod/zero_shot_detector.py:248-250), running on the GPU:
 
     core distances + exact mutual-reachability MST + edge sort   csrc/cluster.hip   (GPU)
-    single linkage / condense / EOM / epsilon / labels           csrc/hdbscan_tree.cpp (host, C++), or -- `hierarchy='device'` --
+    single linkage / condense / selection / epsilon / labels     csrc/hdbscan_tree.cpp (host, C++), or -- `hierarchy='device'` --
                                                                  csrc/hdbscan_device.hip (GPU, the same results bit for bit)
+
+The library's cluster-selection options are taken as the library takes them (semantics of its scikit-learn port,
+sklearn/cluster/_hdbscan/_tree.pyx): `cluster_selection_method` 'eom' (default) or 'leaf', `allow_single_cluster`, `max_cluster_size`
+(None or 0: unlimited; excess of mass only).  Both forms of the hierarchy stage implement them.
 
 `fit` accepts a numpy array (reference call) or a CUDA float32 tensor (fused pipeline).
 """
@@ -17,17 +21,30 @@ import torch
 from ._lib import lib, ptr, stream_ptr, check, CLUSTER_MAX_K
 
 
+def selection_options(cluster_selection_method='eom', allow_single_cluster=False, max_cluster_size=None):
+    """The library's three cluster-selection options -> (selection, allow_single_cluster, max_cluster_size) as vg_hdbscan_tree_host_ex /
+    vg_hdbscan_tree_device_ex take them: 0 = 'eom' / 1 = 'leaf'; 0 / 1; 0 = unlimited (None or 0).  ValueError for anything else."""
+    if cluster_selection_method not in ('eom', 'leaf'):
+        raise ValueError("cluster_selection_method: 'eom' or 'leaf'")
+    if max_cluster_size is not None and int(max_cluster_size) < 0:
+        raise ValueError('max_cluster_size: None, 0 (both: unlimited) or a positive integer')
+    return (1 if cluster_selection_method == 'leaf' else 0, int(bool(allow_single_cluster)), int(max_cluster_size) if max_cluster_size else 0)
+
+
 class HDBSCAN:
     def __init__(self, min_cluster_size=5, min_samples=None, cluster_selection_epsilon=0.0, metric='euclidean',
-                 core_dist_n_jobs=None, max_points=400_000, device='cuda', hierarchy='host', **unused):
+                 core_dist_n_jobs=None, max_points=400_000, device='cuda', hierarchy='host', cluster_selection_method='eom',
+                 allow_single_cluster=False, max_cluster_size=None, **unused):
         if metric != 'euclidean':
             raise NotImplementedError('only the euclidean metric of the reference configuration is implemented')
         for k in unused:
-            if k not in ('alpha', 'algorithm', 'leaf_size', 'approx_min_span_tree', 'gen_min_span_tree',
-                         'cluster_selection_method', 'allow_single_cluster', 'prediction_data', 'memory'):
+            if k not in ('alpha', 'algorithm', 'leaf_size', 'approx_min_span_tree', 'gen_min_span_tree', 'prediction_data', 'memory'):
                 raise TypeError(f'unexpected keyword {k}')
-        if unused.get('cluster_selection_method', 'eom') != 'eom' or unused.get('allow_single_cluster', False):
-            raise NotImplementedError('cluster_selection_method=eom, allow_single_cluster=False only')
+        # (selection, allow_single_cluster, max_cluster_size) as vg_hdbscan_tree_host_ex / _device_ex take them
+        self.selection_args = selection_options(cluster_selection_method, allow_single_cluster, max_cluster_size)
+        self.cluster_selection_method = cluster_selection_method
+        self.allow_single_cluster = bool(allow_single_cluster)
+        self.max_cluster_size = self.selection_args[2] or None
         self.min_cluster_size = int(min_cluster_size)
         self.min_samples = int(min_samples) if min_samples is not None else self.min_cluster_size
         if not 1 <= self.min_samples <= CLUSTER_MAX_K:
@@ -112,16 +129,17 @@ class HDBSCAN:
         probs = np.empty(n, np.float64)
         nc = ctypes.c_int32(0)
         p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
-        check(lib.vg_hdbscan_tree_host(p(lo), p(hi), p(w2), n, self.min_cluster_size, self.cluster_selection_epsilon,
-                                       p(labels), p(probs), ctypes.byref(nc)), 'vg_hdbscan_tree_host')
+        check(lib.vg_hdbscan_tree_host_ex(p(lo), p(hi), p(w2), n, self.min_cluster_size, self.cluster_selection_epsilon,
+                                          *self.selection_args, p(labels), p(probs), ctypes.byref(nc)), 'vg_hdbscan_tree_host_ex')
         return labels, probs, nc.value
+
 
     def tree_device(self, lo, hi, w2, n, stream=None):
         """CUDA sorted MST (as `mst` returns it) -> (labels int32 [n], probabilities float64 [n], n_clusters int32 [1]) CUDA tensors, queued on
         the stream, nothing waited for: the hierarchy stage as kernels (csrc/hdbscan_device.hip), the same results as `tree`."""
         if self._hier is None:
             self._hier = DeviceHierarchy(max_points=self.max_points, device=self.device)
-        return self._hier.tree_async(lo, hi, w2, n, self.min_cluster_size, self.cluster_selection_epsilon, stream)
+        return self._hier.tree_async(lo, hi, w2, n, self.min_cluster_size, self.cluster_selection_epsilon, stream, *self.selection_args)
 
     def fit(self, X, dim=None):
         """numpy input: every column is a clustering coordinate, like the library (3 = `points_ref_wo_ground[..., :3]`,
@@ -171,16 +189,18 @@ class DeviceHierarchy:
             lib.vg_hier_destroy(h)
             self._h = None
 
-    def tree_async(self, lo, hi, w2, n, min_cluster_size, eps, stream=None):
-        """-> (labels, probs, n_clusters) CUDA tensors, queued on `stream` (nothing waited for)."""
+    def tree_async(self, lo, hi, w2, n, min_cluster_size, eps, stream=None, selection=0, allow_single_cluster=0, max_cluster_size=0):
+        """-> (labels, probs, n_clusters) CUDA tensors, queued on `stream` (nothing waited for).  selection: 0 = excess of mass,
+        1 = leaf; max_cluster_size: 0 = unlimited (`HDBSCAN.selection_args`)."""
         dev = self.device
         labels = torch.empty(n, dtype=torch.int32, device=dev)
         probs = torch.empty(n, dtype=torch.float64, device=dev)
         nc = torch.zeros(1, dtype=torch.int32, device=dev)
-        check(lib.vg_hdbscan_tree_device(self._h, ptr(lo), ptr(hi), ptr(w2), int(n), int(min_cluster_size), float(eps), ptr(labels), ptr(probs),
-                                         ptr(nc), stream_ptr(stream)), 'vg_hdbscan_tree_device')
+        check(lib.vg_hdbscan_tree_device_ex(self._h, ptr(lo), ptr(hi), ptr(w2), int(n), int(min_cluster_size), float(eps), int(selection),
+                                            int(allow_single_cluster), int(max_cluster_size or 0), ptr(labels), ptr(probs), ptr(nc),
+                                            stream_ptr(stream)), 'vg_hdbscan_tree_device_ex')
         return labels, probs, nc
 
-    def tree(self, lo, hi, w2, n, min_cluster_size, eps, stream=None):
-        labels, probs, nc = self.tree_async(lo, hi, w2, n, min_cluster_size, eps, stream)
+    def tree(self, lo, hi, w2, n, min_cluster_size, eps, stream=None, selection=0, allow_single_cluster=0, max_cluster_size=0):
+        labels, probs, nc = self.tree_async(lo, hi, w2, n, min_cluster_size, eps, stream, selection, allow_single_cluster, max_cluster_size)
         return labels, probs, int(nc.item())

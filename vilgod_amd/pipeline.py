@@ -886,7 +886,10 @@ class PseudoLabelPipeline:
         if isinstance(labels, torch.Tensor):
             d_labels, d_probs = labels, probs
             n = d_labels.numel()
-            # the hierarchy selects clusters of at least min_cluster_size points: labels 0 .. n / min_cluster_size - 1
+            # the hierarchy selects clusters of at least min_cluster_size points: labels 0 .. n / min_cluster_size - 1.  The bound holds
+            # for every selection option: excess of mass (with or without max_cluster_size) and 'leaf' both select clusters none of
+            # which contains another, each of >= min_cluster_size points; allow_single_cluster adds only the root ALONE (label 0,
+            # also on a frame of fewer than min_cluster_size points: the + 1)
             bound = n // max(self.cluster_model.min_cluster_size, 1) + 1
         else:
             labels = np.asarray(labels)
