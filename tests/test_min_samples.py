@@ -1,5 +1,5 @@
 """`min_samples` (and with it `clustering.model.min_cluster_size`) above 15: exact core distances for 16 <= k <= 64 on the GPU
-(csrc/cluster.hip k_cl_core_blk_k / k_cl_core_far_k), through the C ABI, `HDBSCAN`, the fused pipeline and the CLI.
+(csrc/cluster.hip: k_cl_core_blk with its LDS-heap list and the wave-wide form of k_cl_core_far), through the C ABI, `HDBSCAN`, the fused pipeline and the CLI.
 
 CPU: the oracle stays pinned to scikit-learn for the new range (MST weights bit-identical, tree stages equal on the same linkage);
 the header's VG_CLUSTER_MAX_K.  GPU: squared core distances, MST, labels and probabilities equal to the oracle bit for bit.
@@ -22,6 +22,8 @@ from test_cluster import blob_scene, lidar_scene
 
 PAIRS = [(15, 16), (15, 32), (25, 25), (40, 64), (10, 48)]            # (min_cluster_size, k = min_samples)
 KS = (16, 17, 31, 32, 33, 48, 63, 64)
+SMALL_KS = (1, 8)                                                     # the register list's own convention: the query is entry 0
+SMALL_K_SCENES = ('blob', 'coincident', 'isolated', 'cell3000')
 EPS = 0.15
 
 
@@ -85,10 +87,15 @@ def test_header_declares_max_k_and_library_exports_the_header():
 def test_new_core_distance_kernels_use_no_scratch():
     from vilgod_amd import build
     text = build._device_asm('cluster.hip')
-    for kernel in ('k_cl_core_blk_k', 'k_cl_core_far_k'):
-        names = set(re.findall(r'\.set (\S*%s\S*)\.private_seg_size' % kernel, text))
-        assert len(names) >= 3, (kernel, names)                      # DIM 3, 4, 5 are in the device code
-        assert build.check_scratch('cluster.hip', kernel) == []
+    sizes = dict(re.findall(r'\.set (\S+)\.private_seg_size, (\d+)', text))
+    # the mangled name of every form: phase A with the register list, the LDS heap of 32 and of 64, phase B over 16 lanes and over the wave
+    forms = {'register A': r'k_cl_core_blkILi\dE9ClRegList', 'heap-32 A': r'k_cl_core_blkILi\dE9ClLdsHeapILi32E',
+             'heap-64 A': r'k_cl_core_blkILi\dE9ClLdsHeapILi64E', 'narrow B': r'k_cl_core_farILi\dELb0E', 'wide B': r'k_cl_core_farILi\dELb1E'}
+    for form, pat in forms.items():
+        names = {n for n in sizes if re.search(pat, n)}
+        assert len(names) >= 3, (form, names)                        # DIM 3, 4, 5 are in the device code
+        assert all(int(sizes[n]) == 0 for n in names), (form, {n: sizes[n] for n in names})
+    assert build.check_scratch('cluster.hip', 'k_cl_core_blk') == [] and build.check_scratch('cluster.hip', 'k_cl_core_far') == []
 
 
 # ------------------------------------------------------------------------------------------- GPU
@@ -169,9 +176,10 @@ def _stress_scene(name, k):
 @pytest.mark.parametrize('dim', [3, 4, 5])
 @pytest.mark.parametrize('scene', ['lidar5k', 'lidar40k', 'blob', 'n_le_k', 'n_k_plus_1', 'coincident', 'isolated', 'cell3000'])
 def test_core_distances_equal_oracle(cuda, scene, dim):
-    """k = 15 runs the register kernels (asserted next to the new cases: a dispatch slip shows here), the others the new pair."""
+    """k <= 15 runs the register list and the 16-lane phase B (asserted next to the other cases: a dispatch slip shows here),
+    the others the LDS heap and the wave-wide phase B."""
     import torch
-    for k in (15,) + KS:
+    for k in (SMALL_KS if scene in SMALL_K_SCENES else ()) + (15,) + KS:
         X3 = _scene(scene) if scene in ('lidar5k', 'lidar40k', 'blob') else _stress_scene(scene, k)
         X = _nd(X3, dim)
         n = len(X)

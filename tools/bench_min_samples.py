@@ -6,9 +6,10 @@ one JSON line:
   mst_ms        the whole `HDBSCAN.mst()` call (grid, core distances, Boruvka rounds with their host reads, edge sort): host clock
                 around `reps` back-to-back calls that end in a device synchronise, after 10 warm-up calls; median of `rounds` such
                 measurements, with the rounds' min / max beside it
-  core_ms       the core-distance stage alone = the kernel time of k_cl_blocks + the two cooperative phases (k <= 15: k_cl_core_blk,
-                k_cl_core_far; k >= 16: k_cl_core_blk_k, k_cl_core_far_k) per call, from a kernel trace of the same call sequence in a
-                process of its own per k (`rocprofv3 --kernel-trace`, this file as `--worker`); the same warm-up, median and min / max
+  core_ms       the core-distance stage alone = the kernel time of k_cl_blocks + the two cooperative phases (k_cl_core_blk,
+                k_cl_core_far; k <= 15: register list / 16-lane list, k >= 16: LDS heap / wave-wide list) per call, from a
+                kernel trace of the same call sequence in a process of its own per k (`rocprofv3 --kernel-trace`, this file as
+                `--worker`); the same warm-up, median and min / max
   phase_b_share the share of queries phase A hands to phase B (read from the library's VG_CLUSTER_DEBUG line of one extra call)
 `--k 15` alone uses nothing newer than min_samples <= 15, so the same file measures an older build for comparison.
 """
