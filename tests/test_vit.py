@@ -513,7 +513,7 @@ def test_hip_tower_pair_residual_stream_agrees(cuda, monkeypatch):
 @pytest.mark.parametrize('tower,n', [('VIT_B16', 2), ('VIT_B16', 3), ('VIT_B32', 10), ('VIT_B32', 11)])
 def test_hip_pair_stream_switches_on_at_its_crop_count(cuda, tower, n, monkeypatch):
     """The pair stream (`hl`) and the class-row last block (`cls_only`) both need the compact class-row buffers to fit in the qkv buffer
-    (vg_vit_encode's `cls_fits`): from 3 crops for ViT-B/16, from 11 for ViT-B/32.  Below that count both are off, so VG_VIT_RESID_HL=1
+    (vit_plan's `cls_fits`): from 3 crops for ViT-B/16, from 11 for ViT-B/32.  Below that count both are off, so VG_VIT_RESID_HL=1
     and =0 give bit-identical features; from it on the pair stream runs: the features differ, agree within 5e-4 and keep their distance
     to the fp32 tower (as in test_hip_tower_pair_residual_stream_agrees)."""
     from vilgod_amd.clip_wrapper import VitEncoder
@@ -571,3 +571,106 @@ def test_hip_tower_is_deterministic_with_two_encodes_in_flight(cuda):
     [t.start() for t in th]
     [t.join() for t in th]
     assert not bad, bad
+
+
+# ------------------------------------------------------------------------------- workspace layout, resolved weights
+SMALL_TOWER = dict(width=256, layers=2, heads=4, patch=16, resolution=32, output_dim=64)
+
+
+def _workspace_bytes_closed_form(cfg, dtype, n, fold_on):
+    """vg_vit_workspace_bytes as the header has documented it since the folded LayerNorm: callers allocate by this number."""
+    W, es = cfg['width'], 2 if dtype == 'f16' else 4
+    T = (cfg['resolution'] // cfg['patch']) ** 2 + 1
+
+    def pad(m):
+        return (m + 255) // 256 * 256
+    Mp, Pp, Kp = pad(n * T), pad(n * (T - 1)), (3 * cfg['patch'] ** 2 + 63) // 64 * 64
+    b = (Mp * W * 4                     # residual stream (fp32)
+         + Mp * W * es                  # LayerNorm / attention output
+         + Mp * (3 * W + 256) * es      # qkv (padded row stride)
+         + Mp * 4 * W * es              # hidden activations
+         + Pp * Kp * es                 # patch rows
+         + Pp * W * 4)                  # patch-embedding output (fp32)
+    if fold_on and dtype == 'f16' and W % 256 == 0:
+        b += Mp * W * 2 + Mp * (W // 64) * 8        # fp16 copy of the stream + per-row partial statistics
+    return b + 1024
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('fold_on', [True, False])
+@pytest.mark.parametrize('tower,dtype', [('SMALL', 'f32'), ('SMALL', 'f16'), ('VIT_B16', 'f16'), ('VIT_B32', 'f16'), ('VIT_L14', 'f16')])
+def test_workspace_bytes_formula(cuda, tower, dtype, fold_on, monkeypatch):
+    """The workspace size is part of the ABI (callers allocate by it): it equals the closed form for every tower, with the folded
+    LayerNorm on and off (VG_VIT_LN_FOLD, read when the handle is made), on both sides of every row-tile and class-row boundary."""
+    import ctypes
+    from vilgod_amd._lib import lib, check
+    from vilgod_amd.clip_wrapper import DTYPES
+    cfg = SMALL_TOWER if tower == 'SMALL' else getattr(cw, tower)
+    if not fold_on:
+        monkeypatch.setenv('VG_VIT_LN_FOLD', '0')
+    h = ctypes.c_void_p()
+    check(lib.vg_vit_create(ctypes.byref(h), cfg['width'], cfg['layers'], cfg['heads'], cfg['patch'], cfg['resolution'],
+                            cfg['output_dim'], DTYPES[dtype]), 'vg_vit_create')
+    try:
+        got = {n: lib.vg_vit_workspace_bytes(h, n) for n in (1, 2, 3, 10, 11, 37)}
+    finally:
+        lib.vg_vit_destroy(h)
+    assert got == {n: _workspace_bytes_closed_form(cfg, dtype, n, fold_on) for n in got}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('switches,dtype', [({}, 'f16'), ({'VG_VIT_RESID_HL': '0'}, 'f16'),
+                                            ({'VG_VIT_CLS_LAST': '0', 'VG_VIT_RESID_HL': '0'}, 'f16'), ({'VG_GEMM_W4': '0'}, 'f16'),
+                                            ({'VG_VIT_LN_FOLD': '0'}, 'f16'), ({'VG_VIT_RESID16': '1'}, 'f16'), ({}, 'f32')],
+                         ids=['default', 'hl0', 'cls0-hl0', 'w4-0', 'fold0', 'resid16', 'f32'])
+@pytest.mark.parametrize('tower', ['SMALL', 'VIT_B16'])
+def test_encode_stays_inside_its_workspace(cuda, tower, switches, dtype, monkeypatch):
+    """vg_vit_encode writes nothing behind the vg_vit_workspace_bytes it reports: a guard of 1 MiB behind the workspace (in the same
+    allocation) keeps its byte pattern, and the features equal those from the encoder's own, generously sized workspace -- at 2 and
+    3 crops, the two sides of ViT-B/16's class-row boundary, for every residual-stream form and both kernel families."""
+    from vilgod_amd._lib import lib
+    from vilgod_amd.clip_wrapper import VitEncoder
+    for k, val in switches.items():
+        monkeypatch.setenv(k, val)
+    cfg = SMALL_TOWER if tower == 'SMALL' else cw.VIT_B16
+    enc = VitEncoder(cw.synthetic_vit_weights(3, **cfg), dtype=dtype, device=cuda)
+    guard = 1 << 20
+    for n in (2, 3):
+        x = torch.randn(n, 3, cfg['resolution'], cfg['resolution'], generator=torch.Generator().manual_seed(n)).to(cuda)
+        enc._ws = None
+        want = enc.encode(x).cpu()                                    # workspace sized for n + headroom crops
+        nbytes = lib.vg_vit_workspace_bytes(enc._h, n)
+        buf = torch.zeros(nbytes + guard, dtype=torch.uint8, device=cuda)
+        buf[nbytes:] = 0xA5
+        enc._ws, enc._ws_crops = buf, n
+        got = enc.encode(x).cpu()
+        torch.cuda.synchronize()
+        assert enc._ws is buf
+        assert bool((buf[nbytes:] == 0xA5).all()), f'{tower} n = {n}: encode wrote behind its workspace'
+        assert torch.isfinite(got).all() and torch.equal(got, want)
+
+
+@pytest.mark.gpu
+def test_encode_is_bit_stable_across_weight_reset(cuda):
+    """Setting a block's ln_1.weight again replaces its device tensor (and, with the folded LayerNorm, the tensors derived from it):
+    the same values give bit-equal features, other values give other features -- no encode keeps a pointer or a derived tensor of
+    the replaced one."""
+    import ctypes
+    from vilgod_amd._lib import lib, check
+    from vilgod_amd.clip_wrapper import VitEncoder
+    wd = cw.synthetic_vit_weights(4, **SMALL_TOWER)
+    enc = VitEncoder(wd, dtype='f16', device=cuda)
+    x = torch.randn(3, 3, 32, 32, generator=torch.Generator().manual_seed(3)).to(cuda)
+    name = 'transformer.resblocks.1.ln_1.weight'
+
+    def set_weight(t):
+        t = t.detach().to(torch.float32).contiguous().cpu()
+        with torch.cuda.device(cuda):
+            check(lib.vg_vit_set_weight(enc._h, name.encode(), ctypes.c_void_p(t.data_ptr()), t.numel()), 'vg_vit_set_weight')
+    f0 = enc.encode(x).cpu()
+    set_weight(wd[name])
+    f1 = enc.encode(x).cpu()
+    assert torch.isfinite(f0).all() and torch.equal(f0, f1)
+    set_weight(wd[name] * 1.5 + 0.25)
+    f2 = enc.encode(x).cpu()
+    assert torch.isfinite(f2).all() and not torch.equal(f2, f0)

@@ -29,3 +29,31 @@ static int launch_gemm_pp(const void* X, const void* Wt, const float* bias, void
     return VG_OK;
 }
 
+// The experiments of the development build inside launch_gemm, called at one point (after the profiling pair is open, before the product
+// dispatch).  Returns the result of the launch it ran (or refused) itself, VG_DEV_PASS when the product dispatch is to go on.  May clear
+// *use_pp to send every shape to k_gemm_f16.
+#define VG_DEV_PASS (-1000)
+template <int EPI, int LN>
+static int dev_launch_gemm(vg_vit* v, const void* X, const void* Wt, const float* bias, void* C, float* resid, int M, int N, int K,
+                            hipStream_t st, int ldc, const float* ln_c1, LnPartial* ln_stats, f16* ln_x16, bool* use_pp) {
+    if (getenv("VG_GEMM_V4")) *use_pp = false;          // every shape through k_gemm_f16 (tools/dev/bench_gemm_v4.sh)
+    if constexpr (EPI == EPI_BIAS_RESID_HL || EPI == EPI_BIAS_RESID_H) return VG_DEV_PASS;
+    else {
+        if (v->dtype != 1 || !*use_pp || M % GBM || N % GBN || K % GK) return VG_DEV_PASS;
+        // persistent workgroups (one per CU walking its XCD's run of tiles) per epilogue kind, bit EPI of VG_GEMM_PERSIST.  Alone at
+        // M = 64256: in_proj (+bias) 271 -> 244 us, c_fc (GELU) and out_proj +-0, c_proj -3 %; inside the pipeline no measurable change
+        // (13.65-13.70 ms of GEMMs per frame either way): the next tile's first pieces still wait for the previous tile's stores (one
+        // vmcnt), so only the dispatch gap is saved.
+        static const int persist_mask = getenv("VG_GEMM_PERSIST") ? atoi(getenv("VG_GEMM_PERSIST")) : 0;
+        if constexpr (LN == 0 && (EPI == EPI_BIAS || EPI == EPI_BIAS_GELU || EPI == EPI_BIAS_RESID)) {
+            if ((persist_mask >> EPI) & 1) return launch_gemm_pp64<EPI, false, true>(X, Wt, bias, C, resid, M, N, K, ldc, st);
+        }
+        if (v->gemm_x2 && K % 256 == 0 && (LN != 1 || K / 64 <= X2_LN_MAXP))
+            return launch_gemm_x2<EPI, LN>(X, Wt, bias, C, resid, M, N, K, ldc, st, ln_c1, ln_stats, ln_x16);
+        if (v->gemm_x2 && LN != 0) return VG_ERR_ARG;       // (the two kernels keep different partial statistics)
+        if constexpr (LN == 0 && EPI == EPI_BIAS) {        // k_gemm_f16_w4's ablations and alternative schedules: VG_GEMM_W4 = 1 + VAR
+            if (v->gemm_w4 && K / 64 >= 4) switch (v->gemm_w4) { VG_W4_DEV_CASES(EPI, LN) }
+        }
+        return VG_DEV_PASS;
+    }
+}

@@ -33,6 +33,9 @@
 #include <map>
 #include <atomic>
 #include <mutex>
+#include <memory>
+#include <type_traits>
+#include <assert.h>
 #include <utility>
 
 typedef _Float16 f16;
@@ -1201,23 +1204,50 @@ __global__ __launch_bounds__(64) void k_clip_scores(const float* __restrict__ fe
 }
 
 // ---------------------------------------------------------------------------------------------
+// Environment switches (VG_*): one place that parses them.  env_on: any value that parses to 0 is "off"; unset = `dflt`.
+static int env_int(const char* name, int dflt) { const char* s = getenv(name); return s ? atoi(s) : dflt; }
+static bool env_on(const char* name, bool dflt) { return env_int(name, dflt ? 1 : 0) != 0; }
+
+// Compute units of the current device, queried once per device (one slot per device, like VgPerDeviceOnce in common.h: racing threads
+// store the same value, so no lock).  A device that reports fewer than 8 counts as 256 (MI355X).  The persistent kernels launch one
+// workgroup per CU, rounded up to a multiple of 8: slot s of XCD x = block 8 s + x (vg_persistent_grid).
+static int vg_cu_count() {
+    static std::atomic<int> count[64];
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    std::atomic<int>& slot = count[dev & 63];
+    int n = slot.load(std::memory_order_relaxed);
+    if (!n) {
+        (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
+        if (n < 8) n = 256;
+        slot.store(n, std::memory_order_relaxed);
+    }
+    return n;
+}
+static int vg_persistent_grid(int tiles, int cap) { return ((tiles < cap ? tiles : cap) + 7) / 8 * 8; }
+
+// the fp16 attention's A/B switches: row-major V + transposing LDS reads (VG_ATT_TR), SIMD partners apart in phase (VG_ATT_STAGGER, k_attention_f16 STAG)
+struct AttOptions {
+    bool tr = true, stagger = true;
+    static AttOptions from_env() { return {env_on("VG_ATT_TR", true), env_on("VG_ATT_STAGGER", true)}; }
+};
+
+struct VitWeights;
 #define VG_PROF_MAX 4096
 struct vg_vit {
     int width, layers, heads, patch, res, out_dim, dtype, T;
 #ifdef VG_DEV
-    bool gemm_x2 = getenv("VG_GEMM_X2") ? atoi(getenv("VG_GEMM_X2")) != 0 : false;   // projection GEMMs by k_gemm_f16_x2 (two workgroups per CU)
+    bool gemm_x2 = env_on("VG_GEMM_X2", false);      // projection GEMMs by k_gemm_f16_x2 (two workgroups per CU)
 #endif
-    bool cls_last = !(getenv("VG_VIT_CLS_LAST") && atoi(getenv("VG_VIT_CLS_LAST")) == 0);   // last block: class-token rows only (see vg_vit_encode)
+    bool cls_last = env_on("VG_VIT_CLS_LAST", true);  // last block: class-token rows only (see vit_plan)
     // A/B switches every test exercises (tests/test_vit.py, test_gemm.py), read ONCE when the handle is made -- never per launch: getenv
     // is not safe against a concurrent setenv, the worker threads launch concurrently, and a captured graph must replay what the plain
     // launches of the same handle run.  The handle-less entry points (vg_gemm, vg_gemm_resid_splitk, vg_attention) build a
     // temporary handle per call, i.e. read them per call on the caller's thread.
-    int splitk_max = getenv("VG_GEMM_SPLITK") ? atoi(getenv("VG_GEMM_SPLITK")) : 0;          // opt-in split-K tail of the residual GEMMs (splitk_plan)
-    bool att_tr = !(getenv("VG_ATT_TR") && atoi(getenv("VG_ATT_TR")) == 0);                    // attention: row-major V + transposing LDS reads
-    bool att_stagger = !(getenv("VG_ATT_STAGGER") && atoi(getenv("VG_ATT_STAGGER")) == 0);     // attention: SIMD partners apart in phase (k_attention_f16 STAG)
-    bool f32_mfma = !(getenv("VG_GEMM_F32_MFMA") && atoi(getenv("VG_GEMM_F32_MFMA")) == 0);    // fp32 tower on the matrix cores
-    int gemm_w4 = getenv("VG_GEMM_W4") ? atoi(getenv("VG_GEMM_W4")) : 1;                      // projection GEMMs by k_gemm_f16_w4 (round 6: persistent, 4 waves, assembly K loop); 0: k_gemm_f16_pp64 (a tower uses one family: their LayerNorm partials differ in granularity)
-    int n_cu = 0;                    // compute units of the device the handle works on (set at the first launch)
+    int splitk_max = env_int("VG_GEMM_SPLITK", 0);    // opt-in split-K tail of the residual GEMMs (splitk_plan)
+    AttOptions att = AttOptions::from_env();
+    bool f32_mfma = env_on("VG_GEMM_F32_MFMA", true); // fp32 tower on the matrix cores
+    int gemm_w4 = env_int("VG_GEMM_W4", 1);           // projection GEMMs by k_gemm_f16_w4 (round 6: persistent, 4 waves, assembly K loop); 0: k_gemm_f16_pp64 (a tower uses one family: their LayerNorm partials differ in granularity)
     bool resid_hl = false;           // the residual stream kept as an fp16 PAIR (EPI_BIAS_RESID_HL; round 6, default for the k_gemm_f16_w4 tower with the folded
                                      // LayerNorm and the last block on the class rows; VG_VIT_RESID_HL=0: the fp32 stream): 22 bits of the stream, a third less
                                      // written by out_proj / c_proj -- features 1.8e-4 from the fp32-stream tower's, the same distance to the fp32 tower
@@ -1227,7 +1257,7 @@ struct vg_vit {
     int prof_on = 0, prof_n = 0;
     hipEvent_t prof_ev[2 * VG_PROF_MAX];
     double prof_flops[VG_PROF_MAX];
-    int prof_kind[VG_PROF_MAX];      // 0 = k_gemm_f16 / k_gemm_f32, 1 = k_gemm_f16_pp64 / pp16, 2 / 3 = fp16 attention (all rows / class rows)
+    int prof_kind[VG_PROF_MAX];      // 0 = k_gemm_f16 / k_gemm_f32, 1 = the 256 x 256 kernels (k_gemm_f16_w4 / k_gemm_f16_pp64), 2 / 3 = fp16 attention (all rows / class rows)
     bool prof_init = false;
     std::map<std::string, void*> w;        // device pointers (f32 or f16 depending on role)
     std::map<std::string, size_t> numel;
@@ -1246,6 +1276,9 @@ struct vg_vit {
     std::atomic<uint64_t> weights_gen{0};
     std::mutex mtx;
     std::map<std::string, void*> w32;
+    // the tensors of `w` by role (vit_weights): resolved from the maps once per generation, shared by the encodes in flight
+    std::shared_ptr<const VitWeights> resolved;
+    uint64_t resolved_gen = 0;
 };
 
 static bool is_gemm_weight(const std::string& n) {
@@ -2132,15 +2165,10 @@ static int launch_gemm_pp64(const void* X, const void* Wt, const float* bias, vo
     const int ntn = N / 256;
     int cwt = gemm_chunk_tiles_256(ntn);
 #ifdef VG_DEV
-    if (getenv("VG_GEMM_CW")) { cwt = atoi(getenv("VG_GEMM_CW")); if (cwt < 1 || ntn % cwt) cwt = ntn; }      // tile-order sweep (development build)
+    if (getenv("VG_GEMM_CW")) { cwt = env_int("VG_GEMM_CW", 0); if (cwt < 1 || ntn % cwt) cwt = ntn; }      // tile-order sweep (development build)
 #endif
     int grid = (M / 256) * ntn;
-    if (PERSIST) {
-        static int n_cu = 0;
-        if (!n_cu) { int dev = 0; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev); if (n_cu < 8) n_cu = 256; }
-        if (grid > n_cu) grid = n_cu;
-        grid = (grid + 7) / 8 * 8;                 // slot s of XCD x = block 8 s + x
-    }
+    if (PERSIST) grid = vg_persistent_grid(grid, vg_cu_count());
     hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, st, (const f16*)X, (const f16*)Wt, bias, C, resid, M, N, K,
                        ldc, cwt, trace, ln_c1, ln_stats, ln_x16, 1);
     VG_LAUNCH_CHECK();
@@ -2158,19 +2186,13 @@ static int launch_gemm_w4(const void* X, const void* Wt, const float* bias, void
     const int lds = 5 * 32768;
     VG_MAX_DYNAMIC_LDS(kern, lds);
     const int ntn = N / 256;
-    static std::atomic<int> n_cu_{0};                // persistent grid: one workgroup per CU, a multiple of 8 (slot s of XCD x = block 8 s + x)
-    int n_cu = n_cu_.load();
-    if (!n_cu) { int dev = 0; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev); if (n_cu < 8) n_cu = 256; n_cu_.store(n_cu); }
-    int grid = (M / 256) * ntn;
-    if (grid > n_cu) grid = n_cu;
-#ifdef VG_DEV
-    { static const int cap = getenv("VG_GEMM_W4_GRID") ? atoi(getenv("VG_GEMM_W4_GRID")) : 0; if (cap >= 8 && grid > cap) grid = cap; }   // experiment: two encodes on disjoint CU halves
-#endif
-    grid = (grid + 7) / 8 * 8;
+    int cap = vg_cu_count();                         // persistent grid: one workgroup per CU
     int cwt = gemm_chunk_tiles_256(ntn);
 #ifdef VG_DEV
-    if (getenv("VG_GEMM_CW")) { const int c = atoi(getenv("VG_GEMM_CW")); if (c >= 1 && ntn % c == 0) cwt = c; }      // tile-order sweep (development build; read per launch)
+    { static const int half = env_int("VG_GEMM_W4_GRID", 0); if (half >= 8 && half < cap) cap = half; }   // experiment: two encodes on disjoint CU halves
+    { const int c = env_int("VG_GEMM_CW", 0); if (c >= 1 && ntn % c == 0) cwt = c; }      // tile-order sweep (development build; read per launch)
 #endif
+    const int grid = vg_persistent_grid((M / 256) * ntn, cap);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, (const f16*)X, (const f16*)Wt, bias, C, resid, M, N, K,
                        ldc, cwt, ln_c1, ln_stats, ln_x16, trace);
     VG_LAUNCH_CHECK();
@@ -2201,22 +2223,16 @@ static int launch_gemm_resid_tail(const void* X, const void* Wt, const float* bi
 #include "dev/vit_dev_launchers.inc"
 #endif  // VG_DEV
 
+// Every projection GEMM of the tower and of the test entry points.  fp16, top to bottom: the two fp16-stream epilogues (one kernel family
+// each), then for the ViT shapes (N % 256 == 0, K >= 128) the split-K tail, k_gemm_f16_w4, k_gemm_f16_pp64; k_gemm_f16 serves the
+// remaining legal shapes.  fp32: the MFMA kernel where its tile divides the shape, else the vector-ALU kernel.
 template <int EPI, int LN = 0>
 static int launch_gemm(const vg_vit* cv, const void* X, const void* Wt, const float* bias, void* C, float* resid, int M,
                        int N, int K, hipStream_t st, int ldc = 0, const float* ln_c1 = nullptr, LnPartial* ln_stats = nullptr,
                        f16* ln_x16 = nullptr, float* sk_scratch = nullptr, size_t sk_bytes = 0) {
     if (ldc == 0) ldc = N;
     vg_vit* v = const_cast<vg_vit*>(cv);
-    // f16 ViT shapes (N % 256 == 0, K >= 128) take the ping-pong kernel; k_gemm_f16 serves the remaining legal shapes.
     bool use_pp = v->dtype == 1 && N % 256 == 0 && K % 64 == 0 && K / 64 >= 2;
-#ifdef VG_DEV
-    if (getenv("VG_GEMM_V4")) use_pp = false;          // every shape through k_gemm_f16 (tools/dev/bench_gemm_v4.sh)
-#endif
-    if (!v->n_cu) {
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&v->n_cu, hipDeviceAttributeMultiprocessorCount, dev);
-    }
     const bool prof = v->prof_on && v->prof_n < VG_PROF_MAX;
     if (prof) (void)hipEventRecord(v->prof_ev[2 * v->prof_n], st);
     struct Closer {
@@ -2229,124 +2245,96 @@ static int launch_gemm(const vg_vit* cv, const void* X, const void* Wt, const fl
             }
         }
     } closer{v, prof, st, 2.0 * (double)M * (double)N * (double)K, use_pp ? 1 : 0};
+#ifdef VG_DEV      // the development build's experiments (dev/vit_dev_launchers.inc) may take the launch over or send it to k_gemm_f16
+    { const int rc = dev_launch_gemm<EPI, LN>(v, X, Wt, bias, C, resid, M, N, K, st, ldc, ln_c1, ln_stats, ln_x16, &use_pp); if (rc != VG_DEV_PASS) return rc; }
+    closer.kind = use_pp ? 1 : 0;
+#endif
+    const bool w4 = v->gemm_w4 && K / 64 >= 4;        // (k_gemm_f16_w4's ring wants four K-tiles)
     if constexpr (EPI == EPI_BIAS_RESID_HL) {     // the stream as an fp16 pair: k_gemm_f16_w4's producer epilogue only
-        if (!(LN == 2 && v->dtype == 1 && v->gemm_w4 && use_pp && M % 256 == 0 && K % 64 == 0 && K / 64 >= 4 && resid && ln_x16)) return VG_ERR_ARG;
+        if (!(LN == 2 && use_pp && w4 && M % 256 == 0 && resid && ln_x16)) return VG_ERR_ARG;
         return launch_gemm_w4<EPI, LN>(X, Wt, bias, C, resid, M, N, K, ldc, st, ln_c1, ln_stats, ln_x16);
-    } else
-    if constexpr (EPI == EPI_BIAS_RESID_H) {      // fp16 residual stream: only the 256 x 256 kernel implements it
-        if (!(use_pp && K % 64 == 0 && K / 64 >= 2)) return VG_ERR_ARG;
+    } else if constexpr (EPI == EPI_BIAS_RESID_H) {      // fp16 residual stream: only k_gemm_f16_pp64 implements it
+        if (!use_pp) return VG_ERR_ARG;
         return launch_gemm_pp64<EPI>(X, Wt, bias, C, resid, M, N, K, ldc, st);
-    } else
-    if (v->dtype == 1) {
+    } else if (v->dtype == 1) {
         if (M % GBM || N % GBN || K % GK) return VG_ERR_ARG;
         if (use_pp) {
-            {
-                // experiment (development build only): persistent workgroups (one per CU walking its XCD's run of tiles) per epilogue kind,
-                // bit EPI of VG_GEMM_PERSIST.  Alone at M = 64256: in_proj (+bias) 271 -> 244 us, c_fc (GELU) and out_proj +-0,
-                // c_proj -3 %; inside the pipeline no measurable change (13.65-13.70 ms of GEMMs per frame either way): the next
-                // tile's first pieces still wait for the previous tile's stores (one vmcnt), so only the dispatch gap is saved.
-#ifdef VG_DEV
-                static const int persist_mask = getenv("VG_GEMM_PERSIST") ? atoi(getenv("VG_GEMM_PERSIST")) : 0;
-                if constexpr (LN == 0 && (EPI == EPI_BIAS || EPI == EPI_BIAS_GELU || EPI == EPI_BIAS_RESID)) {
-                    if ((persist_mask >> EPI) & 1) return launch_gemm_pp64<EPI, false, true>(X, Wt, bias, C, resid, M, N, K, ldc, st);
-                }
-#endif
-#ifdef VG_DEV
-                if (v->gemm_x2 && K % 256 == 0 && (LN != 1 || K / 64 <= X2_LN_MAXP))
-                    return launch_gemm_x2<EPI, LN>(X, Wt, bias, C, resid, M, N, K, ldc, st, ln_c1, ln_stats, ln_x16);
-                if (v->gemm_x2 && LN != 0) return VG_ERR_ARG;       // (the two kernels keep different partial statistics)
-#endif
-                if constexpr (EPI == EPI_BIAS_RESID && LN != 1) {
-                    // residual GEMMs with scratch at hand: the row tiles beyond the last complete round of tiles run K-split
-                    if (sk_scratch && M % 256 == 0 && !(v->gemm_w4 && K / 64 >= 4)) {        // (k_gemm_f16_w4 has no tile rounds to fill: persistent workgroups)
-                        const SplitPlan sp = splitk_plan(M / 256, N / 256, K / 64, sk_bytes, v->splitk_max, v->n_cu);
-                        if (sp.parts) {
-                            const int rc = launch_gemm_pp64<EPI, false, false, LN>(X, Wt, bias, C, resid, sp.r_main * 256, N, K, ldc, st, nullptr, ln_c1, ln_stats, ln_x16);
-                            if (rc) return rc;
-                            return launch_gemm_resid_tail<LN>(X, Wt, bias, resid, sp.r_main * 256, M - sp.r_main * 256, N, K, ldc, sp.parts, sk_scratch, st,
-                                                              ln_stats, ln_x16);
-                        }
+            if constexpr (EPI == EPI_BIAS_RESID && LN != 1) {
+                // residual GEMMs with scratch at hand: the row tiles beyond the last complete round of tiles run K-split
+                // (not k_gemm_f16_w4's: persistent workgroups have no tile rounds to fill)
+                if (sk_scratch && M % 256 == 0 && !w4) {
+                    const SplitPlan sp = splitk_plan(M / 256, N / 256, K / 64, sk_bytes, v->splitk_max, vg_cu_count());
+                    if (sp.parts) {
+                        const int rc = launch_gemm_pp64<EPI, false, false, LN>(X, Wt, bias, C, resid, sp.r_main * 256, N, K, ldc, st, nullptr, ln_c1, ln_stats, ln_x16);
+                        if (rc) return rc;
+                        return launch_gemm_resid_tail<LN>(X, Wt, bias, resid, sp.r_main * 256, M - sp.r_main * 256, N, K, ldc, sp.parts, sk_scratch, st,
+                                                          ln_stats, ln_x16);
                     }
                 }
-                if (v->gemm_w4 && K / 64 >= 4) {
-#ifdef VG_DEV
-                    if constexpr (LN == 0 && EPI == EPI_BIAS) {
-                        switch (v->gemm_w4) { VG_W4_DEV_CASES(EPI, LN) }
-                    }
-#endif
-                    return launch_gemm_w4<EPI, LN>(X, Wt, bias, C, resid, M, N, K, ldc, st, ln_c1, ln_stats, ln_x16);
-                }
-                return launch_gemm_pp64<EPI, false, false, LN>(X, Wt, bias, C, resid, M, N, K, ldc, st, nullptr, ln_c1, ln_stats, ln_x16);
             }
+            if (w4) return launch_gemm_w4<EPI, LN>(X, Wt, bias, C, resid, M, N, K, ldc, st, ln_c1, ln_stats, ln_x16);
+            return launch_gemm_pp64<EPI, false, false, LN>(X, Wt, bias, C, resid, M, N, K, ldc, st, nullptr, ln_c1, ln_stats, ln_x16);
         }
-        if (LN != 0) return VG_ERR_ARG;            // the folded LayerNorm exists in the 256 x 256 kernel only
-        int nwg = (M / GBM) * (N / GBN);
+        if (LN != 0) return VG_ERR_ARG;            // the folded LayerNorm exists in the 256 x 256 kernels only
         VG_MAX_DYNAMIC_LDS(k_gemm_f16<EPI>, G_LDS_BYTES);
-        hipLaunchKernelGGL((k_gemm_f16<EPI>), dim3(nwg), dim3(512), G_LDS_BYTES, st, (const f16*)X, (const f16*)Wt, bias, C,
+        hipLaunchKernelGGL((k_gemm_f16<EPI>), dim3((M / GBM) * (N / GBN)), dim3(512), G_LDS_BYTES, st, (const f16*)X, (const f16*)Wt, bias, C,
                            resid, M, N, K, ldc, gemm_chunk_tiles(N, K));
     } else {
         if (M % 64 || N % 64 || K % 16) return VG_ERR_ARG;
-        if (M % 128 == 0 && N % 128 == 0 && v->f32_mfma) {      // (VG_GEMM_F32_MFMA=0: the vector-ALU kernel for every shape, bit-identical)
+        if (M % 128 == 0 && N % 128 == 0 && v->f32_mfma)        // (VG_GEMM_F32_MFMA=0: the vector-ALU kernel for every shape, bit-identical)
             hipLaunchKernelGGL((k_gemm_f32_mfma<EPI>), dim3((M / 128) * (N / 128)), dim3(256), 0, st, (const float*)X, (const float*)Wt, bias,
                                (float*)C, resid, M, N, K);
-        } else {
-            int nwg = (M / 64) * (N / 64);
-            hipLaunchKernelGGL((k_gemm_f32<EPI>), dim3(nwg), dim3(256), 0, st, (const float*)X, (const float*)Wt, bias,
+        else
+            hipLaunchKernelGGL((k_gemm_f32<EPI>), dim3((M / 64) * (N / 64)), dim3(256), 0, st, (const float*)X, (const float*)Wt, bias,
                                (float*)C, resid, M, N, K);
-        }
     }
+    VG_LAUNCH_CHECK();
+    return VG_OK;
+}
+
+// one short-sequence attention launch (T <= AT_MAXT): 7 waves per workgroup, at most 256 persistent workgroups
+struct AttArgs { const f16* qkv; f16* out; int T, W, heads, ld, items; long long* trace; hipStream_t st; int q_tiles; };
+template <bool TRACE, int NKB, int TT = 0, bool TR = false, bool STAG = false>
+static int launch_attention_short(const AttArgs& a) {
+    auto kern = k_attention_f16<TRACE, NKB, TT, TR, STAG>;
+    const int lds = TR ? AT_LDS_BYTES_TR : AT_LDS_BYTES;
+    VG_MAX_DYNAMIC_LDS(kern, lds);
+    hipLaunchKernelGGL(kern, dim3(a.items < 256 ? a.items : 256), dim3(448), lds, a.st, a.qkv, a.out, a.T, a.W, a.heads, a.ld, a.items, a.trace,
+                       a.q_tiles);
     VG_LAUNCH_CHECK();
     return VG_OK;
 }
 
 template <bool TRACE>
 static int launch_attention(const f16* qkv, f16* out, int T, int W, int heads, int ld, int items, long long* trace, hipStream_t st,
-                            int q_tiles = 7, bool tr = true, bool stagger = true) {
+                            int q_tiles = 7, AttOptions opt = AttOptions()) {
     if (T > AT_MAXT && !TRACE) {                 // ViT-L/14 and other long token counts: the flash-style kernel
         if (T > AL_MAXT) return VG_ERR_ARG;
-        static std::atomic<int> n_cu_{0};
-        int n_cu = n_cu_.load();
-        if (!n_cu) { int dev = 0; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev); if (n_cu < 8) n_cu = 256; n_cu_.store(n_cu); }
-        const dim3 grid(items < 2 * n_cu ? items : 2 * n_cu);     // persistent: two workgroups per CU
+        const int cap = 2 * vg_cu_count();       // persistent: two workgroups per CU
         VG_MAX_DYNAMIC_LDS(k_attention_f16_long, AL_LDS_BYTES);
-        hipLaunchKernelGGL(k_attention_f16_long, grid, dim3(256), AL_LDS_BYTES, st, qkv, out, T, W, heads, ld, items, q_tiles);
+        hipLaunchKernelGGL(k_attention_f16_long, dim3(items < cap ? items : cap), dim3(256), AL_LDS_BYTES, st, qkv, out, T, W, heads, ld, items, q_tiles);
         VG_LAUNCH_CHECK();
         return VG_OK;
     }
     const int nkb = (T + 31) / 32;
     if (nkb < 1 || nkb > 7) return VG_ERR_ARG;
-    // ViT-B/16: row-major V + transposing LDS reads (VG_ATT_TR=0: the transposed V image of rounds 1-2; same numbers, 1.6 % slower)
-    // (tr: vg_vit::att_tr of the calling handle; tests run both paths in one process and compare them bit for bit)
-    if (T == 197 && !TRACE && tr && stagger) {
-        const dim3 grid7(items < 256 ? items : 256);
-        VG_MAX_DYNAMIC_LDS((k_attention_f16<false, 7, 197, true, true>), AT_LDS_BYTES_TR);
-        hipLaunchKernelGGL((k_attention_f16<false, 7, 197, true, true>), grid7, dim3(448), AT_LDS_BYTES_TR, st, qkv, out, T, W, heads, ld, items, trace, q_tiles);
-        VG_LAUNCH_CHECK();
-        return VG_OK;
+    const AttArgs a{qkv, out, T, W, heads, ld, items, trace, st, q_tiles};
+    if (T == 197 && !TRACE) {
+        // ViT-B/16: row-major V + transposing LDS reads (VG_ATT_TR=0: the transposed V image of rounds 1-2; same numbers, 1.6 % slower)
+        // (opt: vg_vit::att of the calling handle; tests run the paths in one process and compare them bit for bit)
+        if (opt.tr && opt.stagger) return launch_attention_short<false, 7, 197, true, true>(a);
+        if (opt.tr) return launch_attention_short<false, 7, 197, true>(a);
+        return launch_attention_short<false, 7, 197>(a);
     }
-    if (T == 197 && !TRACE && tr) {
-        const dim3 grid7(items < 256 ? items : 256);
-        VG_MAX_DYNAMIC_LDS((k_attention_f16<false, 7, 197, true>), AT_LDS_BYTES_TR);
-        hipLaunchKernelGGL((k_attention_f16<false, 7, 197, true>), grid7, dim3(448), AT_LDS_BYTES_TR, st, qkv, out, T, W, heads, ld, items, trace, q_tiles);
-        VG_LAUNCH_CHECK();
-        return VG_OK;
+    switch (nkb) {
+        case 1: return launch_attention_short<TRACE, 1>(a);
+        case 2: return launch_attention_short<TRACE, 2>(a);
+        case 3: return launch_attention_short<TRACE, 3>(a);
+        case 4: return launch_attention_short<TRACE, 4>(a);
+        case 5: return launch_attention_short<TRACE, 5>(a);
+        case 6: return launch_attention_short<TRACE, 6>(a);
+        default: return launch_attention_short<TRACE, 7>(a);
     }
-    const dim3 grid(items < 256 ? items : 256), block(448);
-#define VG_ATT(N)                                                                                                                  \
-    case N: {                                                                                                                      \
-        VG_MAX_DYNAMIC_LDS((k_attention_f16<TRACE, N>), AT_LDS_BYTES);                                                              \
-        hipLaunchKernelGGL((k_attention_f16<TRACE, N>), grid, block, AT_LDS_BYTES, st, qkv, out, T, W, heads, ld, items, trace, q_tiles);   \
-        break; }
-    if (T == 197 && !TRACE) {                  // ViT-B/16
-        VG_MAX_DYNAMIC_LDS((k_attention_f16<false, 7, 197>), AT_LDS_BYTES);
-        hipLaunchKernelGGL((k_attention_f16<false, 7, 197>), grid, block, AT_LDS_BYTES, st, qkv, out, T, W, heads, ld, items, trace, q_tiles);
-        VG_LAUNCH_CHECK();
-        return VG_OK;
-    }
-    switch (nkb) { VG_ATT(1) VG_ATT(2) VG_ATT(3) VG_ATT(4) VG_ATT(5) VG_ATT(6) VG_ATT(7) }
-#undef VG_ATT
-    VG_LAUNCH_CHECK();
-    return VG_OK;
 }
 
 // W'[n,k] = f16(g[k] * W[n,k]);  c1[n] = sum_k W'[n,k] (of the ROUNDED values, which is what the MFMAs will sum);
@@ -2378,6 +2366,68 @@ static void* vit_w(const vg_vit* v, const std::string& n) {
     return it == v->w.end() ? nullptr : it->second;
 }
 
+// ---- the tower's tensors by role.  One table of a block's state_dict names serves the resolver and vit_fold_ln.
+enum { LN1_W, LN1_B, IN_W, IN_B, OUT_W, OUT_B, LN2_W, LN2_B, FC_W, FC_B, PROJ_W, PROJ_B, N_BLOCK_TENSORS };
+static const char* const kBlockTensor[N_BLOCK_TENSORS] = {"ln_1.weight", "ln_1.bias", "attn.in_proj_weight", "attn.in_proj_bias",
+                                                          "attn.out_proj.weight", "attn.out_proj.bias", "ln_2.weight", "ln_2.bias",
+                                                          "mlp.c_fc.weight", "mlp.c_fc.bias", "mlp.c_proj.weight", "mlp.c_proj.bias"};
+static std::string block_prefix(int l) { return "transformer.resblocks." + std::to_string(l) + "."; }
+
+struct FoldedLn { const void* w; const float *c1, *c2; };      // "<weight>#ln", "#c1", "#c2": a LayerNorm folded into the GEMM behind it (vit_fold_ln)
+struct BlockWeights {
+    const void* t[N_BLOCK_TENSORS];
+    FoldedLn in_proj, c_fc;                                    // (null unless vg_vit::ln_fold)
+    const float* f(int i) const { return (const float*)t[i]; }
+};
+struct TopWeights {
+    const void *conv1, *conv1_1ch;                             // (#1ch: vit_fold_conv1, null until an input_kind 3 encode)
+    const float *cls, *pos, *pos_1ch, *ln_pre_w, *ln_pre_b, *ln_post_w, *ln_post_b, *proj;
+};
+struct VitWeights { TopWeights top; std::vector<BlockWeights> blocks; };
+
+// fills `out` from the handle's maps (caller holds v->mtx); a tensor that was never set is reported by name
+static int vit_resolve(const vg_vit* v, VitWeights* out) {
+    bool ok = true, told = false;
+    auto get = [&](const std::string& n, auto& slot, bool required) {
+        slot = static_cast<std::remove_reference_t<decltype(slot)>>(vit_w(v, n));
+        if (slot || !required) return;
+        if (!told && n.find('#') == std::string::npos) { fprintf(stderr, "[vilgod_hip] vg_vit_encode: weight %s not set\n", n.c_str()); told = true; }
+        ok = false;
+    };
+    TopWeights& t = out->top;
+    get("conv1.weight", t.conv1, true);       get("class_embedding", t.cls, true);     get("positional_embedding", t.pos, true);
+    get("ln_pre.weight", t.ln_pre_w, true);   get("ln_pre.bias", t.ln_pre_b, true);
+    get("ln_post.weight", t.ln_post_w, true); get("ln_post.bias", t.ln_post_b, true);  get("proj", t.proj, true);
+    get("conv1.weight#1ch", t.conv1_1ch, false);
+    get("positional_embedding#1ch", t.pos_1ch, false);
+    out->blocks.resize((size_t)v->layers);
+    for (int l = 0; l < v->layers; ++l) {
+        BlockWeights& b = out->blocks[l];
+        const std::string p = block_prefix(l);
+        for (int i = 0; i < N_BLOCK_TENSORS; ++i) get(p + kBlockTensor[i], b.t[i], true);
+        for (FoldedLn* f : {&b.in_proj, &b.c_fc}) {
+            const std::string wn = p + kBlockTensor[f == &b.in_proj ? IN_W : FC_W];
+            get(wn + "#ln", f->w, v->ln_fold); get(wn + "#c1", f->c1, v->ln_fold); get(wn + "#c2", f->c2, v->ln_fold);
+        }
+    }
+    return ok ? VG_OK : VG_ERR_ARG;
+}
+
+// the handle's tensors by role, resolved again only after one of them was replaced (weights_gen moved)
+static int vit_weights(vg_vit* v, std::shared_ptr<const VitWeights>* out) {
+    std::lock_guard<std::mutex> lock(v->mtx);
+    const uint64_t gen = v->weights_gen.load();
+    if (!v->resolved || v->resolved_gen != gen) {
+        auto w = std::make_shared<VitWeights>();
+        const int rc = vit_resolve(v, w.get());
+        if (rc) return rc;
+        v->resolved = w;
+        v->resolved_gen = gen;
+    }
+    *out = v->resolved;
+    return VG_OK;
+}
+
 /* Builds the derived tensors of the folded LayerNorms once per handle (and again after a weight was replaced).  Called at the top
  * of vg_vit_encode; allocates and synchronises, so the first encode of a handle must not run inside a stream capture
  * (vg_vit_classify_graph runs it as plain launches). */
@@ -2387,15 +2437,14 @@ static int vit_fold_ln(vg_vit* v, hipStream_t st) {
     if (v->fold_ready.load()) return VG_OK;
     const int W = v->width;
     for (int l = 0; l < v->layers; ++l) {
-        const std::string p = "transformer.resblocks." + std::to_string(l) + ".";
-        const char* sets[2][4] = {{"ln_1.weight", "ln_1.bias", "attn.in_proj_weight", "attn.in_proj_bias"},
-                                  {"ln_2.weight", "ln_2.bias", "mlp.c_fc.weight", "mlp.c_fc.bias"}};
+        const std::string p = block_prefix(l);
+        const int sets[2][4] = {{LN1_W, LN1_B, IN_W, IN_B}, {LN2_W, LN2_B, FC_W, FC_B}};      // LayerNorm gain, shift; the GEMM's weight, bias
         for (int k = 0; k < 2; ++k) {
-            const std::string wn = p + sets[k][2];
+            const std::string wn = p + kBlockTensor[sets[k][2]];
             auto it32 = v->w32.find(wn);
-            const float* g = (const float*)vit_w(v, p + sets[k][0]);
-            const float* be = (const float*)vit_w(v, p + sets[k][1]);
-            const float* b = (const float*)vit_w(v, p + sets[k][3]);
+            const float* g = (const float*)vit_w(v, p + kBlockTensor[sets[k][0]]);
+            const float* be = (const float*)vit_w(v, p + kBlockTensor[sets[k][1]]);
+            const float* b = (const float*)vit_w(v, p + kBlockTensor[sets[k][3]]);
             if (it32 == v->w32.end() || !g || !be || !b) continue;      // vg_vit_encode reports the missing weight by name
             const int N = (int)(v->numel[wn] / (size_t)W);
             for (const char* suffix : {"#ln", "#c1", "#c2"}) {
@@ -2499,9 +2548,8 @@ int vg_vit_create(vg_vit** out, int width, int layers, int heads, int patch, int
     v->width = width; v->layers = layers; v->heads = heads; v->patch = patch; v->res = resolution;
     v->out_dim = out_dim; v->dtype = dtype; v->T = T;
     v->resid_h = dtype == 1 && width % 256 == 0 && getenv("VG_VIT_RESID16");
-    const char* fold = getenv("VG_VIT_LN_FOLD");
-    v->ln_fold = dtype == 1 && width % 256 == 0 && !v->resid_h && !(fold && atoi(fold) == 0);
-    { const char* hl = getenv("VG_VIT_RESID_HL"); v->resid_hl = v->ln_fold && v->gemm_w4 && v->cls_last && width <= 1024 && !(hl && atoi(hl) == 0); }
+    v->ln_fold = dtype == 1 && width % 256 == 0 && !v->resid_h && env_on("VG_VIT_LN_FOLD", true);
+    v->resid_hl = v->ln_fold && v->gemm_w4 && v->cls_last && width <= 1024 && env_on("VG_VIT_RESID_HL", true);
 #ifdef VG_DEV
     if (getenv("VG_GEMM_V4")) v->resid_h = v->ln_fold = false;      // (k_gemm_f16 has neither epilogue)
 #endif
@@ -2532,6 +2580,7 @@ int vg_vit_set_weight(vg_vit* v, const char* name, const float* h_data, int64_t 
     if (it != v->w.end()) {
         (void)hipFree(it->second);
         v->w.erase(it);
+        v->weights_gen.fetch_add(1);             // (no resolved pointer to the freed tensor survives an early return below)
     }
     if (v->dtype == 1 && (n == "conv1.weight" || n == "positional_embedding")) {
         v->conv1_ready.store(false);             // the single-channel patch embedding's derived tensors are rebuilt at the next encode
@@ -2610,265 +2659,304 @@ __global__ __launch_bounds__(256) void k_scatter_cls_q(const f16* __restrict__ q
 
 static int64_t pad128(int64_t m) { return (m + 255) / 256 * 256; }   // GEMM row tile (256)
 
-/* bytes of zero-initialised device workspace vg_vit_encode needs for n_crops */
-int64_t vg_vit_workspace_bytes(const vg_vit* v, int n_crops) {
-    if (!v || n_crops <= 0) return 0;
-    int64_t Mp = pad128((int64_t)n_crops * v->T), W = v->width, es = v->dtype == 1 ? 2 : 4;
-    int64_t Pp = pad128((int64_t)n_crops * (v->T - 1)), Kp = vit_kpad(v);
-    int64_t b = Mp * W * 4            // x (f32)
-                + Mp * W * es         // h
-                + Mp * (3 * W + 256) * es   // qkv (padded row stride)
-                + Mp * 4 * W * es     // mlp
-                + Pp * Kp * es        // patches
-                + Pp * W * 4;         // patch-embed output (f32)
-    if (v->ln_fold) b += Mp * W * 2 + Mp * (W / 64) * 8;      // fp16 copy of the residual + per-row partial statistics (folded LayerNorm)
-    return b + 1024;
-}
+}  // extern "C"
 
-/* input_kind 0: f32 CHW crops [n,3,res,res]; 1: f16 CHW crops; d_feat: [n,out_dim] f32 */
-int vg_vit_encode(vg_vit* v, const void* d_crops, int input_kind, int n_crops, void* d_workspace, float* d_feat,
-                  void* stream) {
-    if (!v || !d_crops || !d_workspace || !d_feat || n_crops <= 0 || input_kind < 0 || input_kind > 3) return VG_ERR_ARG;
+// ---- the plan of one encode: every size, the form of the residual stream and the byte offset of every workspace region, computed once
+// per call from (handle, n_crops, input_kind).  vg_vit_workspace_bytes reports plan.total; vg_vit_encode takes its pointers from the
+// same offsets.
+enum class Stream {
+    F32,         // fp32 in region x; separate LayerNorm launches write h
+    F32_FOLD,    // fp32 in region x; the LayerNorms ride in the GEMMs around them: out_proj / c_proj also write the fp16 copy x16 and the rows' partial statistics
+    PAIR,        // an fp16 pair (EPI_BIAS_RESID_HL): hi = x16 (what in_proj / c_fc read anyway), lo in region x; LayerNorms folded; 22 bits of the stream
+    F16          // fp16 in region x (VG_VIT_RESID16), separate LayerNorm launches
+};
+struct Carve {                                  // consecutive regions of a buffer
+    int64_t at = 0;
+    int64_t take(int64_t bytes) { const int64_t o = at; at += bytes; return o; }
+};
+// The last block's compact class-token rows (Mc = n_crops padded to the row tile).  Both layouts borrow a region that is dead at the time:
+struct ClsTail { int64_t xc, hc, x16c, mlpc, stats, size; };        // inside qkv, after the attention: fp32 stream rows, attention rows, fp16 copy, hidden activations, row statistics
+struct ClsQuery { int64_t x16, q, stats, size; };                   // inside mlp, before the attention: fp16 stream rows, their projected queries, row statistics
+struct VitPlan {
+    int64_t M, Mp, P, Pp, Kp, Mc;               // tokens, patches (p: padded to the row tile), K of the patch embedding (padded to 64), class rows
+    int embed_k;                                // K the patch-embedding GEMM runs with (input_kind 3: patch^2, the folded single-channel weight)
+    int qkv_ld;                                 // row stride of the qkv buffer in elements
+    int nst;                                    // partial statistics per row the folded LayerNorm's producers write
+    Stream stream;
+    bool ln1_in_embed;                          // k_embed_lnpre also writes ln_1 of block 0 into h
+    bool cls_only_last;                         // the last block runs its tail on the class-token rows only
+    int64_t x, h, qkv, mlp, patches, pe, x16, lnst, total;      // byte offsets of the regions; the workspace's size
+    int64_t pe_bytes;                           // (pe is dead once the embedding kernel has run: scratch of the residual GEMMs' split-K tails)
+    ClsTail tail;
+    ClsQuery query;
+};
+
+static int vit_plan(const vg_vit* v, int n_crops, int input_kind, VitPlan* out) {
+    if (!v || n_crops <= 0 || input_kind < 0 || input_kind > 3) return VG_ERR_ARG;
     if (input_kind >= 2 && v->dtype != 1) return VG_ERR_ARG;
     if (input_kind == 3 && (v->patch * v->patch) % 128) return VG_ERR_ARG;       // K of the folded patch embedding: two 64-wide K-tiles at least
     if (input_kind == 2 && vit_kpad(v) != 3 * v->patch * v->patch) return VG_ERR_ARG; // renderer patch rows carry no K padding
-    hipStream_t st = (hipStream_t)stream;
-    const int W = v->width, T = v->T, L = v->layers, H = v->heads;
-    const int64_t M = (int64_t)n_crops * T, Mp = pad128(M), es = v->dtype == 1 ? 2 : 4;
-    const int64_t P = (int64_t)n_crops * (T - 1), Pp = pad128(P), Kp = vit_kpad(v);     // patch-embedding K, padded to 64
-    char* ws = (char*)d_workspace;
-    float* x = (float*)ws;            ws += Mp * W * 4;
-    void* h = ws;                     ws += Mp * W * es;
+    VitPlan p;
+    const int64_t W = v->width, es = v->dtype == 1 ? 2 : 4;
+    p.M = (int64_t)n_crops * v->T;        p.Mp = pad128(p.M);
+    p.P = (int64_t)n_crops * (v->T - 1);  p.Pp = pad128(p.P);
+    p.Kp = vit_kpad(v);                   p.Mc = pad128(n_crops);
+    p.embed_k = input_kind == 3 ? v->patch * v->patch : (int)p.Kp;
     // fp16: qkv rows padded by 64 halves.  The padding dates from k_gemm_f16, where 4608-byte rows aliased on the memory channels
     // (+20 %); with k_gemm_f16_pp64 the GEMM time no longer depends on it (13.50-13.58 ms per frame for 0 / 32 / 64 / 128 / 256),
     // but whole frames run 2.5 % faster with 0-128 than with 256 halves (57.0 vs 55.3 frames/s): less to write and to stride over.
-    const int qkv_ld = v->dtype == 1 ? 3 * W + 64 : 3 * W;
-    void* qkv = ws;                   ws += Mp * (3 * W + 256) * es;
-    void* mlp = ws;                   ws += Mp * 4 * W * es;
-    void* patches = ws;               ws += Pp * Kp * es;
-    float* pe = (float*)ws;           ws += Pp * W * 4;
-    const size_t pe_bytes = (size_t)(Pp * W * 4);      // dead once the embedding kernel has run: scratch of the residual GEMMs' split-K tails
-    const bool fold = v->ln_fold;
-    f16* x16 = (f16*)ws;              if (fold) ws += Mp * W * 2;
-    LnPartial* lnst = (LnPartial*)ws;
-    if (fold) { const int frc = vit_fold_ln(v, st); if (frc) return frc; }
-    if (input_kind == 3) { const int frc = vit_fold_conv1(v, st); if (frc) return frc; }
+    // (The region keeps room for 256.)
+    p.qkv_ld = v->dtype == 1 ? 3 * (int)W + 64 : 3 * (int)W;
+    p.nst = v->gemm_w4 ? (int)W >> 7 : (int)W >> 8;           // per 128 columns (k_gemm_f16_w4) or per 256 (k_gemm_f16_pp64)
+    const bool fold = v->ln_fold;                             // (vg_vit_create: fp16 tower, width % 256 == 0, not the fp16 stream)
+    const int64_t stats_row = (W / 64) * (int64_t)sizeof(LnPartial);     // room for W / 64 partials per row (k_gemm_f16_x2's count)
+    Carve ws;
+    p.x = ws.take(p.Mp * W * 4);
+    p.h = ws.take(p.Mp * W * es);
+    const int64_t qkv_bytes = p.Mp * (3 * W + 256) * es, mlp_bytes = p.Mp * 4 * W * es;
+    p.qkv = ws.take(qkv_bytes);
+    p.mlp = ws.take(mlp_bytes);
+    p.patches = ws.take(p.Pp * p.Kp * es);
+    p.pe_bytes = p.Pp * W * 4;
+    p.pe = ws.take(p.pe_bytes);
+    p.x16 = ws.take(fold ? p.Mp * W * 2 : 0);
+    p.lnst = ws.take(fold ? p.Mp * stats_row : 0);
+    p.total = ws.at + 1024;
+    Carve t, q;
+    p.tail.xc = t.take(p.Mc * W * 4);     p.tail.hc = t.take(p.Mc * W * 2);   p.tail.x16c = t.take(p.Mc * W * 2);
+    p.tail.mlpc = t.take(p.Mc * 4 * W * 2);
+    p.tail.stats = t.take(p.Mc * stats_row);
+    p.tail.size = t.at;
+    p.query.x16 = q.take(p.Mc * W * 2);   p.query.q = q.take(p.Mc * W * 2);   p.query.stats = q.take(p.Mc * stats_row);
+    p.query.size = q.at;
+    // The last block runs on the compact class-token rows only if their buffers fit in the regions they borrow.  With ViT-B/16 that holds
+    // from 3 crops, ViT-B/32 from 11, ViT-L/14 from 2 (tests/test_vit.py pins the boundary).
+    const bool cls_fits = p.tail.size <= qkv_bytes && p.query.size <= mlp_bytes;
+    p.cls_only_last = v->cls_last && fold && v->layers > 1 && cls_fits;
+    // every full-row residual GEMM of the pair stream is a folded-LayerNorm producer and no kernel reads the pair as the tower's output, so
+    // it needs the last block on the compact fp32 class rows (vg_vit_create: resid_hl implies cls_last); otherwise the fp32 stream stays
+    const bool pair = v->resid_hl && fold && p.cls_only_last;
+    p.stream = v->resid_h ? Stream::F16 : pair ? Stream::PAIR : fold ? Stream::F32_FOLD : Stream::F32;
+    p.ln1_in_embed = !v->resid_h && v->dtype == 1 && v->layers > 0;
+    assert(p.stream != Stream::PAIR || p.cls_only_last);
+    *out = p;
+    return VG_OK;
+}
 
-    auto need = [&](const std::string& n) -> void* {
-        auto it = v->w.find(n);
-        return it == v->w.end() ? nullptr : it->second;
-    };
-    const char* top[] = {"conv1.weight", "class_embedding", "positional_embedding", "ln_pre.weight", "ln_pre.bias",
-                         "ln_post.weight", "ln_post.bias", "proj"};
-    for (const char* n : top)
-        if (!need(n)) {
-            fprintf(stderr, "[vilgod_hip] vg_vit_encode: weight %s not set\n", n);
-            return VG_ERR_ARG;
-        }
-    // im2col (skipped when the renderer already wrote patch rows)
-    if (input_kind >= 2) patches = const_cast<void*>(d_crops);
-    else {
-        int blocks = (int)((P * Kp + 255) / 256);
-        if (blocks > 65535 * 8) blocks = 65535 * 8;
-        if (v->dtype == 1) {
-            if (input_kind == 0)
-                hipLaunchKernelGGL((k_im2col<float, f16>), dim3(blocks), dim3(256), 0, st, (const float*)d_crops, (f16*)patches, n_crops, v->res, v->patch, (int)Kp);
-            else
-                hipLaunchKernelGGL((k_im2col<f16, f16>), dim3(blocks), dim3(256), 0, st, (const f16*)d_crops, (f16*)patches, n_crops, v->res, v->patch, (int)Kp);
-        } else {
-            if (input_kind == 0)
-                hipLaunchKernelGGL((k_im2col<float, float>), dim3(blocks), dim3(256), 0, st, (const float*)d_crops, (float*)patches, n_crops, v->res, v->patch, (int)Kp);
-            else
-                hipLaunchKernelGGL((k_im2col<f16, float>), dim3(blocks), dim3(256), 0, st, (const f16*)d_crops, (float*)patches, n_crops, v->res, v->patch, (int)Kp);
-        }
-        VG_LAUNCH_CHECK();
-    }
-    // input_kind 3: single-channel patch rows [P, patch^2] times the folded K = patch^2 weight; its constant rides in the positional table
-    const float* pos_tab = (const float*)need(input_kind == 3 ? "positional_embedding#1ch" : "positional_embedding");
-    int rc = input_kind == 3 ? launch_gemm<EPI_NONE_F32>(v, patches, need("conv1.weight#1ch"), nullptr, pe, nullptr, (int)Pp, W, v->patch * v->patch, st)
-                             : launch_gemm<EPI_NONE_F32>(v, patches, need("conv1.weight"), nullptr, pe, nullptr, (int)Pp, W, (int)Kp, st);
-    if (rc) return rc;
-    if (!pos_tab) return VG_ERR_ARG;
-    const bool rh = v->resid_h;
-    bool ln1_done = false;
-    f16* xh = (f16*)x;                // the residual stream lives in the same workspace region, as fp16 when `rh`
-    // The last block runs on the compact class-token rows (`cls_only` below) only if their buffers fit in the qkv buffer (statistics sized
-    // like vg_vit_workspace_bytes: W / 64 partials per row, k_gemm_f16_x2's count).  With ViT-B/16 that holds from 3 crops, ViT-B/32 from
-    // 11, ViT-L/14 from 2 (tests/test_vit.py pins the boundary).
-    const int64_t Mc = pad128(n_crops);
-    const bool cls_fits = Mc * W * 16 + Mc * (W / 64) * 8 <= Mp * (3 * W + 256) * es;
-    // the stream as an fp16 pair (VG_VIT_RESID_HL): hi = x16 (what in_proj / c_fc read anyway), lo in the fp32 stream's region; every full-row
-    // residual GEMM is then a folded-LayerNorm producer (the last block runs on the compact fp32 class rows: hence `cls_fits`)
-    const bool hl = v->resid_hl && fold && !rh && v->dtype == 1 && L > 1 && W % 256 == 0 && cls_fits;
-    f16* xlo = (f16*)x;
-    if (rh)
-        hipLaunchKernelGGL((k_embed_lnpre<f16>), dim3((unsigned)((Mp + 3) / 4)), dim3(256), 0, st, pe, (const float*)need("class_embedding"),
-                           pos_tab, (const float*)need("ln_pre.weight"),
-                           (const float*)need("ln_pre.bias"), xh, (int)M, T, W, (int)Mp);
-    else {
-        // fp16 tower: ln_1 of block 0 is computed by the same kernel (writes h next to x)
-        ln1_done = v->dtype == 1 && L > 0;
-        const float* lw1 = ln1_done ? (const float*)need("transformer.resblocks.0.ln_1.weight") : nullptr;
-        const float* lb1 = ln1_done ? (const float*)need("transformer.resblocks.0.ln_1.bias") : nullptr;
-        if (ln1_done && (!lw1 || !lb1)) return VG_ERR_ARG;
-        hipLaunchKernelGGL((k_embed_lnpre<float>), dim3((unsigned)((Mp + 3) / 4)), dim3(256), 0, st, pe, (const float*)need("class_embedding"),
-                           pos_tab, (const float*)need("ln_pre.weight"),
-                           (const float*)need("ln_pre.bias"), x, (int)M, T, W, (int)Mp, lw1, lb1, ln1_done ? (f16*)h : (f16*)nullptr,
-                           hl ? (f16*)x16 : (f16*)nullptr, hl ? xlo : (f16*)nullptr);
-    }
-    VG_LAUNCH_CHECK();
-    for (int l = 0; l < L; ++l) {
-        std::string p = "transformer.resblocks." + std::to_string(l) + ".";
-        const char* names[] = {"ln_1.weight", "ln_1.bias", "attn.in_proj_weight", "attn.in_proj_bias", "attn.out_proj.weight",
-                               "attn.out_proj.bias", "ln_2.weight", "ln_2.bias", "mlp.c_fc.weight", "mlp.c_fc.bias",
-                               "mlp.c_proj.weight", "mlp.c_proj.bias"};
-        void* wp[12];
-        for (int i = 0; i < 12; ++i) {
-            wp[i] = need(p + names[i]);
-            if (!wp[i]) {
-                fprintf(stderr, "[vilgod_hip] vg_vit_encode: weight %s%s not set\n", p.c_str(), names[i]);
-                return VG_ERR_ARG;
+// ---- one encode: the handle, its plan and resolved tensors, the stream, and the workspace regions as pointers
+struct VitRun {
+    vg_vit* v; const VitPlan& p; const TopWeights& top; hipStream_t st; int n_crops; char* ws;
+    int W() const { return v->width; }
+    float* x() const { return (float*)(ws + p.x); }                 // F16: fp16 rows; PAIR: the lo halves
+    f16* x_h() const { return (f16*)(ws + p.x); }
+    void* h() const { return ws + p.h; }
+    void* qkv() const { return ws + p.qkv; }
+    void* mlp() const { return ws + p.mlp; }
+    float* pe() const { return (float*)(ws + p.pe); }
+    f16* x16() const { return (f16*)(ws + p.x16); }
+    LnPartial* lnst() const { return (LnPartial*)(ws + p.lnst); }
+    bool folded() const { return p.stream == Stream::F32_FOLD || p.stream == Stream::PAIR; }
+
+    // patches (im2col unless the renderer already wrote patch rows) -> patch embedding -> class token, positions, ln_pre [, ln_1 of block 0]
+    int embed(const void* d_crops, int input_kind, const BlockWeights* b0) const {
+        const void* patches = d_crops;
+        if (input_kind < 2) {
+            void* out = ws + p.patches;
+            patches = out;
+            int blocks = (int)((p.P * p.Kp + 255) / 256);
+            if (blocks > 65535 * 8) blocks = 65535 * 8;
+            const int res = v->res, ps = v->patch, Kp = (int)p.Kp;
+            if (v->dtype == 1) {
+                if (input_kind == 0) hipLaunchKernelGGL((k_im2col<float, f16>), dim3(blocks), dim3(256), 0, st, (const float*)d_crops, (f16*)out, n_crops, res, ps, Kp);
+                else hipLaunchKernelGGL((k_im2col<f16, f16>), dim3(blocks), dim3(256), 0, st, (const f16*)d_crops, (f16*)out, n_crops, res, ps, Kp);
+            } else {
+                if (input_kind == 0) hipLaunchKernelGGL((k_im2col<float, float>), dim3(blocks), dim3(256), 0, st, (const float*)d_crops, (float*)out, n_crops, res, ps, Kp);
+                else hipLaunchKernelGGL((k_im2col<f16, float>), dim3(blocks), dim3(256), 0, st, (const f16*)d_crops, (float*)out, n_crops, res, ps, Kp);
             }
-        }
-        void *fw1 = nullptr, *fw2 = nullptr;
-        const float *f1c1 = nullptr, *f1c2 = nullptr, *f2c1 = nullptr, *f2c2 = nullptr;
-        if (fold) {
-            fw1 = need(p + "attn.in_proj_weight#ln"); f1c1 = (const float*)need(p + "attn.in_proj_weight#c1"); f1c2 = (const float*)need(p + "attn.in_proj_weight#c2");
-            fw2 = need(p + "mlp.c_fc.weight#ln");     f2c1 = (const float*)need(p + "mlp.c_fc.weight#c1");     f2c2 = (const float*)need(p + "mlp.c_fc.weight#c2");
-            if (!fw1 || !f1c1 || !f1c2 || !fw2 || !f2c1 || !f2c2) return VG_ERR_ARG;
-        }
-        if (l == 0 && ln1_done) {
-            // h already holds ln_1(x) of block 0 (k_embed_lnpre)
-        } else if (fold) {
-            // ln_1 rides in in_proj: raw fp16 residual (x16) and row statistics (lnst) from the previous block's c_proj epilogue
-        } else if (rh)
-            hipLaunchKernelGGL((k_layernorm<f16, f16>), dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, (const f16*)xh, (const float*)wp[0], (const float*)wp[1], (f16*)h, (int)M, W, 1);
-        else if (v->dtype == 1)
-            hipLaunchKernelGGL((k_layernorm<f16>), dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, x, (const float*)wp[0], (const float*)wp[1], (f16*)h, (int)M, W, 1);
-        else
-            hipLaunchKernelGGL((k_layernorm<float>), dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, x, (const float*)wp[0], (const float*)wp[1], (float*)h, (int)M, W, 1);
-        VG_LAUNCH_CHECK();
-        // The LAST block: only the class token's row of its output is ever read (ln_post(x[:, 0, :]) @ proj, model.py:235-238), and
-        // after the attention every row is processed on its own (out_proj, ln_2, c_fc, QuickGELU, c_proj and the two residual adds).
-        // So the block computes all keys and values, the class token's attention row, and then runs its three remaining GEMMs on
-        // the n_crops class-token rows alone (compacted, padded to the row tile) instead of on n_crops x T rows: the same value
-        // per element -- a row's dot products do not depend on which rows share its tile -- for 1 / T of the work.
-        const bool cls_only = v->cls_last && fold && !rh && l == L - 1 && L > 1 && cls_fits;     // (the compact buffers live in the qkv buffer)
-        if (hl && l == L - 1 && !cls_only) return VG_ERR_ARG;          // the pair stream has no full-row last block (resid_hl implies cls_last)
-        if (cls_only && W % 256 == 0) {
-            // ... and of in_proj's three thirds that block needs K and V for every row but Q for the class-token rows only (round 5: a
-            // third of the launch, 270 -> ~190 us per frame): in_proj's K / V rows (weight rows [W, 3W)) over all tokens, its Q rows over
-            // the compacted class-token rows (the MLP buffer is free here), the queries scattered back to where the attention reads
-            // them.  The other tokens' Q columns keep block L - 2's values: the attention's first query tile computes rows from them
-            // that nobody reads (a query row never meets another query row).  Same kernel, same K loop per row: the same bits.
-            const int nst = v->gemm_w4 ? W >> 7 : W >> 8;        // partial statistics per row: per 128 columns (k_gemm_f16_w4) or per 256
-            char* cb = (char*)mlp;
-            f16* x16q = (f16*)cb;              cb += Mc * W * 2;
-            f16* qc = (f16*)cb;                cb += Mc * W * 2;
-            LnPartial* lnq = (LnPartial*)cb;
-            rc = launch_gemm<EPI_BIAS, 1>(v, x16, (const f16*)fw1 + (size_t)W * W, f1c2 + W, (f16*)qkv + W, nullptr, (int)Mp, 2 * W, W, st, qkv_ld,
-                                          f1c1 + W, lnst);
-            if (rc) return rc;
-            hipLaunchKernelGGL(k_gather_cls_ln, dim3((unsigned)Mc), dim3(256), 0, st, (const f16*)x16, (const LnPartial*)lnst, x16q, lnq, n_crops, T, W, nst);
             VG_LAUNCH_CHECK();
-            rc = launch_gemm<EPI_BIAS, 1>(v, x16q, fw1, f1c2, qc, nullptr, (int)Mc, W, W, st, 0, f1c1, lnq);
-            if (rc) return rc;
-            hipLaunchKernelGGL(k_scatter_cls_q, dim3((unsigned)n_crops), dim3(256), 0, st, (const f16*)qc, (f16*)qkv, T, W, qkv_ld);
-            VG_LAUNCH_CHECK();
-        } else
-        if (fold && !(l == 0 && ln1_done))
-            rc = launch_gemm<EPI_BIAS, 1>(v, x16, fw1, f1c2, qkv, nullptr, (int)Mp, 3 * W, W, st, qkv_ld, f1c1, lnst);
-        else
-            rc = launch_gemm<EPI_BIAS>(v, h, wp[2], (const float*)wp[3], qkv, nullptr, (int)Mp, 3 * W, W, st, qkv_ld);
+        }
+        // input_kind 3: single-channel patch rows [P, patch^2] times the folded K = patch^2 weight; its constant rides in the positional table
+        const bool one_ch = input_kind == 3;
+        const int rc = launch_gemm<EPI_NONE_F32>(v, patches, one_ch ? top.conv1_1ch : top.conv1, nullptr, pe(), nullptr, (int)p.Pp, W(), p.embed_k, st);
         if (rc) return rc;
-        if (v->dtype == 1) {
-            {
-                // measurement hook (vg_vit_profile_read_kind 2 / 3): an event pair around each attention launch
-                const bool aprof = v->prof_on && v->prof_n < VG_PROF_MAX;
-                if (aprof) (void)hipEventRecord(v->prof_ev[2 * v->prof_n], st);
-                rc = launch_attention<false>((const f16*)qkv, (f16*)h, T, W, H, qkv_ld, n_crops * H, nullptr, st, cls_only ? 1 : (T + 31) / 32, v->att_tr, v->att_stagger);
-                if (rc) return rc;
-                if (aprof) {
-                    (void)hipEventRecord(v->prof_ev[2 * v->prof_n + 1], st);
-                    v->prof_kind[v->prof_n] = cls_only ? 3 : 2;
-                    v->prof_flops[v->prof_n++] = 4.0 * (cls_only ? 1.0 : (double)T) * (double)T * 64.0 * (double)(n_crops * H);
-                }
-            }
-        } else {
-            size_t lds = ((size_t)T * 65 + (size_t)T * 64 + 16 * (size_t)T) * sizeof(float);
-            static bool attr = false;
-            if (!attr) {
-                VG_CHECK(hipFuncSetAttribute((const void*)k_attention_f32, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                attr = true;
-            }
-            hipLaunchKernelGGL(k_attention_f32, dim3(n_crops * H), dim3(256), lds, st, (const float*)qkv, (float*)h, T, W, H);
+        const float* pos = one_ch ? top.pos_1ch : top.pos;
+        const dim3 grid((unsigned)((p.Mp + 3) / 4));
+        if (p.stream == Stream::F16)
+            hipLaunchKernelGGL((k_embed_lnpre<f16>), grid, dim3(256), 0, st, pe(), top.cls, pos, top.ln_pre_w, top.ln_pre_b, x_h(), (int)p.M, v->T, W(), (int)p.Mp);
+        else {
+            // fp16 tower: ln_1 of block 0 is computed by the same kernel (writes h next to x); PAIR: it writes the pair instead of fp32 rows
+            const bool ln1 = p.ln1_in_embed, pair = p.stream == Stream::PAIR;
+            hipLaunchKernelGGL((k_embed_lnpre<float>), grid, dim3(256), 0, st, pe(), top.cls, pos, top.ln_pre_w, top.ln_pre_b, x(), (int)p.M, v->T, W(),
+                               (int)p.Mp, ln1 ? b0->f(LN1_W) : (const float*)nullptr, ln1 ? b0->f(LN1_B) : (const float*)nullptr,
+                               ln1 ? (f16*)h() : (f16*)nullptr, pair ? x16() : (f16*)nullptr, pair ? x_h() : (f16*)nullptr);
         }
         VG_LAUNCH_CHECK();
-        if (cls_only) {
-            // compact buffers inside the qkv buffer (dead once the attention has run): residual rows, attention rows, fp16 copy, hidden
-            // activations, row statistics
-            char* cb = (char*)qkv;
-            float* xc = (float*)cb;            cb += Mc * W * 4;
-            f16* hc = (f16*)cb;                cb += Mc * W * 2;
-            f16* x16c = (f16*)cb;              cb += Mc * W * 2;
-            f16* mlpc = (f16*)cb;              cb += Mc * 4 * W * 2;
-            LnPartial* lnc = (LnPartial*)cb;
-            hipLaunchKernelGGL(k_gather_cls, dim3((unsigned)Mc), dim3(256), 0, st, (const f16*)h, (const float*)x, hc, xc, n_crops, T, W,
-                               hl ? (const f16*)x16 : (const f16*)nullptr, hl ? (const f16*)xlo : (const f16*)nullptr);
-            VG_LAUNCH_CHECK();
-            rc = launch_gemm<EPI_BIAS_RESID, 2>(v, hc, wp[4], (const float*)wp[5], nullptr, xc, (int)Mc, W, W, st, 0, nullptr, lnc, x16c);
-            if (rc) return rc;
-            rc = launch_gemm<EPI_BIAS_GELU, 1>(v, x16c, fw2, f2c2, mlpc, nullptr, (int)Mc, 4 * W, W, st, 0, f2c1, lnc);
-            if (rc) return rc;
-            rc = launch_gemm<EPI_BIAS_RESID>(v, mlpc, wp[10], (const float*)wp[11], nullptr, xc, (int)Mc, W, 4 * W, st);
-            if (rc) return rc;
-            hipLaunchKernelGGL((k_head<float>), dim3(n_crops), dim3(256), W * sizeof(float), st, (const float*)xc, (const float*)need("ln_post.weight"),
-                               (const float*)need("ln_post.bias"), (const float*)need("proj"), d_feat, 1, W, v->out_dim);
+        return VG_OK;
+    }
+
+    // h = LayerNorm(stream); nothing to launch where the LayerNorm rides in the GEMM behind it
+    int layernorm(const float* lw, const float* lb) const {
+        const dim3 grid((unsigned)((p.M + 3) / 4));
+        if (folded()) return VG_OK;
+        if (p.stream == Stream::F16) hipLaunchKernelGGL((k_layernorm<f16, f16>), grid, dim3(256), 0, st, (const f16*)x_h(), lw, lb, (f16*)h(), (int)p.M, W(), 1);
+        else if (v->dtype == 1) hipLaunchKernelGGL((k_layernorm<f16>), grid, dim3(256), 0, st, (const float*)x(), lw, lb, (f16*)h(), (int)p.M, W(), 1);
+        else hipLaunchKernelGGL((k_layernorm<float>), grid, dim3(256), 0, st, (const float*)x(), lw, lb, (float*)h(), (int)p.M, W(), 1);
+        VG_LAUNCH_CHECK();
+        return VG_OK;
+    }
+
+    // stream += X @ Wt^T + bias over all rows (out_proj, c_proj).  `producer`: a folded LayerNorm reads the result, so the epilogue also
+    // writes the fp16 copy and the rows' partial statistics (the last block's c_proj has no such consumer: ln_post reads fp32 rows in k_head)
+    int resid_gemm(const void* X, const void* Wt, const float* bias, int K, bool producer) const {
+        const int Mp = (int)p.Mp;
+        if (p.stream == Stream::F16) return launch_gemm<EPI_BIAS_RESID_H>(v, X, Wt, bias, nullptr, x(), Mp, W(), K, st);
+        if (p.stream == Stream::PAIR && producer) return launch_gemm<EPI_BIAS_RESID_HL, 2>(v, X, Wt, bias, nullptr, x(), Mp, W(), K, st, 0, nullptr, lnst(), x16());
+        if (folded() && producer) return launch_gemm<EPI_BIAS_RESID, 2>(v, X, Wt, bias, nullptr, x(), Mp, W(), K, st, 0, nullptr, lnst(), x16(), pe(), (size_t)p.pe_bytes);
+        return launch_gemm<EPI_BIAS_RESID>(v, X, Wt, bias, nullptr, x(), Mp, W(), K, st, 0, nullptr, nullptr, nullptr, pe(), (size_t)p.pe_bytes);
+    }
+
+    // qkv = ln_1(stream) @ in_proj^T + bias.  ln_done: h already holds ln_1 (block 0 after k_embed_lnpre, or layernorm() on an unfolded stream)
+    int in_proj(const BlockWeights& b, bool ln_done) const {
+        const int Mp = (int)p.Mp;
+        if (ln_done) return launch_gemm<EPI_BIAS>(v, h(), b.t[IN_W], b.f(IN_B), qkv(), nullptr, Mp, 3 * W(), W(), st, p.qkv_ld);
+        // ln_1 rides in in_proj: raw fp16 residual (x16) and row statistics (lnst) from the previous block's c_proj epilogue
+        return launch_gemm<EPI_BIAS, 1>(v, x16(), b.in_proj.w, b.in_proj.c2, qkv(), nullptr, Mp, 3 * W(), W(), st, p.qkv_ld, b.in_proj.c1, lnst());
+    }
+
+    // The last block on the class rows needs K and V for every row but Q for the class-token rows only (round 5: a third of the launch,
+    // 270 -> ~190 us per frame): in_proj's K / V rows (weight rows [W, 3W)) over all tokens, its Q rows over the compacted class-token
+    // rows (the MLP buffer is free here), the queries scattered back to where the attention reads them.  The other tokens' Q columns keep
+    // block L - 2's values: the attention's first query tile computes rows from them that nobody reads (a query row never meets another
+    // query row).  Same kernel, same K loop per row: the same bits.
+    int in_proj_cls(const BlockWeights& b) const {
+        const int w = W(), Mc = (int)p.Mc;
+        const FoldedLn& f = b.in_proj;
+        char* cb = (char*)mlp();
+        f16 *x16q = (f16*)(cb + p.query.x16), *qc = (f16*)(cb + p.query.q);
+        LnPartial* lnq = (LnPartial*)(cb + p.query.stats);
+        int rc = launch_gemm<EPI_BIAS, 1>(v, x16(), (const f16*)f.w + (size_t)w * w, f.c2 + w, (f16*)qkv() + w, nullptr, (int)p.Mp, 2 * w, w, st, p.qkv_ld, f.c1 + w, lnst());
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_gather_cls_ln, dim3((unsigned)Mc), dim3(256), 0, st, (const f16*)x16(), (const LnPartial*)lnst(), x16q, lnq, n_crops, v->T, w, p.nst);
+        VG_LAUNCH_CHECK();
+        rc = launch_gemm<EPI_BIAS, 1>(v, x16q, f.w, f.c2, qc, nullptr, Mc, w, w, st, 0, f.c1, lnq);
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_scatter_cls_q, dim3((unsigned)n_crops), dim3(256), 0, st, (const f16*)qc, (f16*)qkv(), v->T, w, p.qkv_ld);
+        VG_LAUNCH_CHECK();
+        return VG_OK;
+    }
+
+    // h = attention(qkv); cls: the class token's query row only (the first query tile)
+    int attention(bool cls) const {
+        const int T = v->T, H = v->heads;
+        if (v->dtype != 1) {
+            const size_t lds = ((size_t)T * 65 + (size_t)T * 64 + 16 * (size_t)T) * sizeof(float);
+            VG_MAX_DYNAMIC_LDS(k_attention_f32, 160 * 1024);
+            hipLaunchKernelGGL(k_attention_f32, dim3(n_crops * H), dim3(256), lds, st, (const float*)qkv(), (float*)h(), T, W(), H);
             VG_LAUNCH_CHECK();
             return VG_OK;
         }
-        rc = rh ? launch_gemm<EPI_BIAS_RESID_H>(v, h, wp[4], (const float*)wp[5], nullptr, x, (int)Mp, W, W, st)
-           : hl ? launch_gemm<EPI_BIAS_RESID_HL, 2>(v, h, wp[4], (const float*)wp[5], nullptr, (float*)xlo, (int)Mp, W, W, st, 0, nullptr, lnst, x16)
-           : fold ? launch_gemm<EPI_BIAS_RESID, 2>(v, h, wp[4], (const float*)wp[5], nullptr, x, (int)Mp, W, W, st, 0, nullptr, lnst, x16, pe, pe_bytes)
-                  : launch_gemm<EPI_BIAS_RESID>(v, h, wp[4], (const float*)wp[5], nullptr, x, (int)Mp, W, W, st, 0, nullptr, nullptr, nullptr, pe, pe_bytes);
+        // measurement hook (vg_vit_profile_read_kind 2 / 3): an event pair around each attention launch
+        const bool aprof = v->prof_on && v->prof_n < VG_PROF_MAX;
+        if (aprof) (void)hipEventRecord(v->prof_ev[2 * v->prof_n], st);
+        const int rc = launch_attention<false>((const f16*)qkv(), (f16*)h(), T, W(), H, p.qkv_ld, n_crops * H, nullptr, st, cls ? 1 : (T + 31) / 32, v->att);
         if (rc) return rc;
-        if (fold) {
-            // ln_2 rides in c_fc
-        } else if (rh)
-            hipLaunchKernelGGL((k_layernorm<f16, f16>), dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, (const f16*)xh, (const float*)wp[6], (const float*)wp[7], (f16*)h, (int)M, W, 1);
-        else if (v->dtype == 1)
-            hipLaunchKernelGGL((k_layernorm<f16>), dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, x, (const float*)wp[6], (const float*)wp[7], (f16*)h, (int)M, W, 1);
-        else
-            hipLaunchKernelGGL((k_layernorm<float>), dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, x, (const float*)wp[6], (const float*)wp[7], (float*)h, (int)M, W, 1);
-        VG_LAUNCH_CHECK();
-        rc = fold ? launch_gemm<EPI_BIAS_GELU, 1>(v, x16, fw2, f2c2, mlp, nullptr, (int)Mp, 4 * W, W, st, 0, f2c1, lnst)
-                  : launch_gemm<EPI_BIAS_GELU>(v, h, wp[8], (const float*)wp[9], mlp, nullptr, (int)Mp, 4 * W, W, st);
-        if (rc) return rc;
-        // the last block's c_proj has no LayerNorm consumer in a GEMM (ln_post reads the class token's fp32 row in k_head)
-        rc = rh ? launch_gemm<EPI_BIAS_RESID_H>(v, mlp, wp[10], (const float*)wp[11], nullptr, x, (int)Mp, W, 4 * W, st)
-           : (hl && l + 1 < L) ? launch_gemm<EPI_BIAS_RESID_HL, 2>(v, mlp, wp[10], (const float*)wp[11], nullptr, (float*)xlo, (int)Mp, W, 4 * W, st, 0, nullptr, lnst, x16)
-           : (fold && l + 1 < L) ? launch_gemm<EPI_BIAS_RESID, 2>(v, mlp, wp[10], (const float*)wp[11], nullptr, x, (int)Mp, W, 4 * W, st, 0, nullptr, lnst, x16, pe, pe_bytes)
-                  : launch_gemm<EPI_BIAS_RESID>(v, mlp, wp[10], (const float*)wp[11], nullptr, x, (int)Mp, W, 4 * W, st, 0, nullptr, nullptr, nullptr, pe, pe_bytes);
-        if (rc) return rc;
+        if (aprof) {
+            (void)hipEventRecord(v->prof_ev[2 * v->prof_n + 1], st);
+            v->prof_kind[v->prof_n] = cls ? 3 : 2;
+            v->prof_flops[v->prof_n++] = 4.0 * (cls ? 1.0 : (double)T) * (double)T * 64.0 * (double)(n_crops * H);
+        }
+        return VG_OK;
     }
-    if (rh)
-        hipLaunchKernelGGL((k_head<f16>), dim3(n_crops), dim3(256), W * sizeof(float), st, (const f16*)xh, (const float*)need("ln_post.weight"),
-                           (const float*)need("ln_post.bias"), (const float*)need("proj"), d_feat, T, W, v->out_dim);
-    else
-        hipLaunchKernelGGL((k_head<float>), dim3(n_crops), dim3(256), W * sizeof(float), st, x, (const float*)need("ln_post.weight"),
-                           (const float*)need("ln_post.bias"), (const float*)need("proj"), d_feat, T, W, v->out_dim);
-    VG_LAUNCH_CHECK();
-    return VG_OK;
+
+    // the rest of a block over all rows: out_proj, ln_2, c_fc + QuickGELU, c_proj
+    int tail_full(const BlockWeights& b, bool last) const {
+        int rc = resid_gemm(h(), b.t[OUT_W], b.f(OUT_B), W(), true);
+        if (rc) return rc;
+        if ((rc = layernorm(b.f(LN2_W), b.f(LN2_B)))) return rc;
+        rc = folded() ? launch_gemm<EPI_BIAS_GELU, 1>(v, x16(), b.c_fc.w, b.c_fc.c2, mlp(), nullptr, (int)p.Mp, 4 * W(), W(), st, 0, b.c_fc.c1, lnst())
+                      : launch_gemm<EPI_BIAS_GELU>(v, h(), b.t[FC_W], b.f(FC_B), mlp(), nullptr, (int)p.Mp, 4 * W(), W(), st);
+        if (rc) return rc;
+        return resid_gemm(mlp(), b.t[PROJ_W], b.f(PROJ_B), 4 * W(), !last);
+    }
+
+    // The LAST block: only the class token's row of its output is ever read (ln_post(x[:, 0, :]) @ proj, model.py:235-238), and
+    // after the attention every row is processed on its own (out_proj, ln_2, c_fc, QuickGELU, c_proj and the two residual adds).
+    // So the block computes all keys and values, the class token's attention row, and then runs its three remaining GEMMs on
+    // the n_crops class-token rows alone (compacted, padded to the row tile) instead of on n_crops x T rows: the same value
+    // per element -- a row's dot products do not depend on which rows share its tile -- for 1 / T of the work.  Ends with the head.
+    int tail_cls(const BlockWeights& b, float* d_feat) const {
+        const int w = W(), Mc = (int)p.Mc;
+        const bool pair = p.stream == Stream::PAIR;
+        char* cb = (char*)qkv();                 // (dead once the attention has run)
+        float* xc = (float*)(cb + p.tail.xc);
+        f16 *hc = (f16*)(cb + p.tail.hc), *x16c = (f16*)(cb + p.tail.x16c), *mlpc = (f16*)(cb + p.tail.mlpc);
+        LnPartial* lnc = (LnPartial*)(cb + p.tail.stats);
+        hipLaunchKernelGGL(k_gather_cls, dim3((unsigned)Mc), dim3(256), 0, st, (const f16*)h(), (const float*)x(), hc, xc, n_crops, v->T, w,
+                           pair ? (const f16*)x16() : (const f16*)nullptr, pair ? (const f16*)x_h() : (const f16*)nullptr);
+        VG_LAUNCH_CHECK();
+        int rc = launch_gemm<EPI_BIAS_RESID, 2>(v, hc, b.t[OUT_W], b.f(OUT_B), nullptr, xc, Mc, w, w, st, 0, nullptr, lnc, x16c);
+        if (rc) return rc;
+        rc = launch_gemm<EPI_BIAS_GELU, 1>(v, x16c, b.c_fc.w, b.c_fc.c2, mlpc, nullptr, Mc, 4 * w, w, st, 0, b.c_fc.c1, lnc);
+        if (rc) return rc;
+        rc = launch_gemm<EPI_BIAS_RESID>(v, mlpc, b.t[PROJ_W], b.f(PROJ_B), nullptr, xc, Mc, w, 4 * w, st);
+        if (rc) return rc;
+        return head(xc, 1, d_feat);
+    }
+
+    // features = ln_post(class-token rows) @ proj; rows_per_crop: distance between two crops' class rows
+    template <typename TI>
+    int head(const TI* rows, int rows_per_crop, float* d_feat) const {
+        hipLaunchKernelGGL((k_head<TI>), dim3(n_crops), dim3(256), W() * sizeof(float), st, rows, top.ln_post_w, top.ln_post_b, top.proj, d_feat,
+                           rows_per_crop, W(), v->out_dim);
+        VG_LAUNCH_CHECK();
+        return VG_OK;
+    }
+};
+
+extern "C" {
+
+/* bytes of zero-initialised device workspace vg_vit_encode needs for n_crops */
+int64_t vg_vit_workspace_bytes(const vg_vit* v, int n_crops) {
+    VitPlan p;
+    return vit_plan(v, n_crops, 0, &p) == VG_OK ? p.total : 0;
+}
+
+/* input_kind 0: f32 CHW crops [n,3,res,res]; 1: f16 CHW crops; 2: patch rows; 3: single-channel patch rows; d_feat: [n,out_dim] f32 */
+int vg_vit_encode(vg_vit* v, const void* d_crops, int input_kind, int n_crops, void* d_workspace, float* d_feat,
+                  void* stream) {
+    if (!d_crops || !d_workspace || !d_feat) return VG_ERR_ARG;
+    VitPlan p;
+    int rc = vit_plan(v, n_crops, input_kind, &p);
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if ((rc = vit_fold_ln(v, st))) return rc;
+    if (input_kind == 3 && (rc = vit_fold_conv1(v, st))) return rc;
+    std::shared_ptr<const VitWeights> w;
+    if ((rc = vit_weights(v, &w))) return rc;
+    if (input_kind == 3 && (!w->top.conv1_1ch || !w->top.pos_1ch)) return VG_ERR_ARG;
+    const VitRun r{v, p, w->top, st, n_crops, (char*)d_workspace};
+    const int L = v->layers;
+    if ((rc = r.embed(d_crops, input_kind, L ? &w->blocks[0] : nullptr))) return rc;
+    for (int l = 0; l < L; ++l) {
+        const BlockWeights& b = w->blocks[l];
+        const bool last = l == L - 1, cls = last && p.cls_only_last, ln1_done = l == 0 && p.ln1_in_embed;
+        assert(!(last && p.stream == Stream::PAIR) || cls);        // the pair stream has no full-row last block (vit_plan)
+        if (!ln1_done && (rc = r.layernorm(b.f(LN1_W), b.f(LN1_B)))) return rc;
+        if ((rc = cls ? r.in_proj_cls(b) : r.in_proj(b, ln1_done || !r.folded()))) return rc;
+        if ((rc = r.attention(cls))) return rc;
+        if (cls) return r.tail_cls(b, d_feat);
+        if ((rc = r.tail_full(b, last))) return rc;
+    }
+    return p.stream == Stream::F16 ? r.head(r.x_h(), v->T, d_feat) : r.head(r.x(), v->T, d_feat);
 }
 
 /* k_attention_f16 alone: softmax(q k^T / 8) v per (crop, head) on the padded qkv rows in_proj writes (model.py:175-187 via
  * nn.MultiheadAttention); exposed so that the kernel can be unit-tested against a plain fp32 attention. */
 int vg_attention(const void* d_qkv, void* d_out, int n_crops, int T, int W, int heads, int ld, void* stream) {
     if (!d_qkv || !d_out || n_crops <= 0 || T < 1 || T > AL_MAXT || heads * 64 != W) return VG_ERR_ARG;
-    const char* tr_env = getenv("VG_ATT_TR");           // handle-less test entry point: read per call, on the caller's thread
-    const char* sg_env = getenv("VG_ATT_STAGGER");
+    // (handle-less test entry point: the switches are read per call, on the caller's thread)
     return launch_attention<false>((const f16*)d_qkv, (f16*)d_out, T, W, heads, ld, n_crops * heads, nullptr, (hipStream_t)stream, (T + 31) / 32,
-                                   !(tr_env && atoi(tr_env) == 0), !(sg_env && atoi(sg_env) == 0));
+                                   AttOptions::from_env());
 }
 
 /* Every attention path of the tower, alone (test entry point; header: vilgod_hip.h).  dtype 1: launch_attention with the caller's q_tiles
@@ -2879,17 +2967,15 @@ int vg_attention_rows(int dtype, const void* d_qkv, void* d_out, int n_crops, in
     hipStream_t st = (hipStream_t)stream;
     if (dtype == 1) {
         if (ld % 8) return VG_ERR_ARG;                  // (16-byte loads of the rows)
-        const char* tr_env = getenv("VG_ATT_TR");       // read per call, on the caller's thread, as vg_attention does
-        const char* sg_env = getenv("VG_ATT_STAGGER");
         return launch_attention<false>((const f16*)d_qkv, (f16*)d_out, T, W, heads, ld, n_crops * heads, nullptr, st, q_tiles,
-                                       !(tr_env && atoi(tr_env) == 0), !(sg_env && atoi(sg_env) == 0));
+                                       AttOptions::from_env());       // (read per call, as vg_attention does)
     }
     if (dtype != 0) return VG_ERR_ARG;
     // k_attention_f32 hard-codes ld = 3 W and computes every row; its K, V and probability rows must fit the LDS it requests (vg_vit_create)
     if (ld != 3 * W || q_tiles != (T + 31) / 32) return VG_ERR_ARG;
     const size_t lds = ((size_t)T * 65 + (size_t)T * 64 + 16 * (size_t)T) * sizeof(float);
     if (lds > 160 * 1024) return VG_ERR_ARG;
-    VG_CHECK(hipFuncSetAttribute((const void*)k_attention_f32, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    VG_MAX_DYNAMIC_LDS(k_attention_f32, 160 * 1024);
     hipLaunchKernelGGL(k_attention_f32, dim3(n_crops * heads), dim3(256), lds, st, (const float*)d_qkv, (float*)d_out, T, W, heads);
     VG_LAUNCH_CHECK();
     return VG_OK;
@@ -2952,7 +3038,7 @@ int vg_gemm_ln_partial_cols(void) {
 
 /* vg_gemm epi 2 (dtype 1) with scratch for the split-K tail (launch_gemm / splitk_plan): what the tower's residual GEMMs run.  Row tiles
  * beyond the last complete round of n_cu tiles are computed K-split through d_scratch (>= 2 MB per tail tile; without enough the
- * launch is not split).  Opt-in: VG_GEMM_SPLITK=n (at most n parts per tile; 8) in the environment, read per launch. */
+ * launch is not split).  Opt-in: VG_GEMM_SPLITK=n (at most n parts per tile; 8) in the environment, read per call (the temporary handle). */
 int vg_gemm_resid_splitk(const void* d_X, const void* d_Wt, const float* d_bias, float* d_resid, int M, int N, int K,
                          void* d_scratch, int64_t scratch_bytes, void* stream) {
     if (!d_X || !d_Wt || !d_bias || !d_resid || scratch_bytes < 0) return VG_ERR_ARG;
@@ -2976,7 +3062,7 @@ int vg_vit_profile(vg_vit* v, int on) {
 }
 
 /* synchronises, then returns the number of GEMM launches sampled, their summed duration (ms) and algorithmic FLOPs;
- * kind -1: every projection GEMM, 0: k_gemm_f16 / k_gemm_f32, 1: k_gemm_f16_pp64 (pp16 when K % 64 != 0) */
+ * kind -1: every projection GEMM, 0: k_gemm_f16 / k_gemm_f32, 1: the 256 x 256 kernels (k_gemm_f16_w4 / k_gemm_f16_pp64) */
 int vg_vit_profile_read_kind(vg_vit* v, int kind, int32_t* h_launches, double* h_ms, double* h_flops) {
     if (!v || !h_launches || !h_ms || !h_flops) return VG_ERR_ARG;
     *h_launches = 0; *h_ms = 0; *h_flops = 0;
