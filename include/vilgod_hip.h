@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-int vg_abi_version(void);
+int vg_abi_version(void);    /* 2: vg_cluster_boxes reports hulls beyond its capacity (d_aux3, below) instead of a partial fit */
 
 /* ---- renderer (rows D1-D6) ------------------------------------------------------------------
  * Replaces the per-cluster loop src/vilgod/zero_shot_detector.py:389-409 and the CLIP
@@ -392,7 +392,10 @@ int vg_plane_ransac(const float* d_points, int stride, const int32_t* d_index, i
 /* Detection.filter with the three active filters of tools/configs/preprocessor/waymo.yaml:16-49
  * (src/dataclass/objects.py:158-181; src/utils/cluster_utils.py:14-15 number_points, :48-49 height,
  * :51-60 plane_distance; all `and` + `required`).  Clusters = segments of d_index (packed point indices into
- * d_points).  d_stats6[c] = {n, zmin, zmax, dmin, dmax, height}; d_valid[c] = 0/1. */
+ * d_points).  d_stats6[c] = {n, zmin, zmax, dmin, dmax, height}; d_valid[c] = 0/1.  Thresholds are inclusive on both sides.
+ * Plane distance = (((a x + b y) + c z) + d) / sqrt((a^2 + b^2) + c^2) in float64 (the plane need not be unit length), its extremes
+ * rounded to float32 in d_stats6.  An empty segment keeps the reductions' identities (zmin = dmin = +inf, zmax = dmax = -inf,
+ * height = -inf, n = 0) and is not valid; vg_cluster_filter_ex does the same. */
 int vg_cluster_filter(const float* d_points, int stride, const int32_t* d_index, const int32_t* d_seg_off, int n_clusters,
                       const double* d_plane4, int min_points, int max_points, double max_min_height, double min_max_height,
                       double min_height, double max_height, float* d_stats6, uint8_t* d_valid, void* stream);
@@ -449,8 +452,21 @@ int vg_cluster_filter_ex(const float* d_points, int stride, const int32_t* d_ind
 
 /* fit_bounding_boxes_simple, static branch (src/vilgod/zero_shot_detector.py:444-462) with
  * method minimum_bounding_rectangle (pointcloud_utils.py:309-372): d_box7[c] = {cx,cy,cz,l,w,h+0.3,rz} float64 in
- * the frame of d_points; d_aux3[c] = {hull vertices, rectangle area, degenerate flag}.  All hull edges are tried
- * (the reference omits the closing edge of qhull's vertex cycle, :329-330). */
+ * the frame of d_points.  All hull edges are tried (the reference omits the closing edge of qhull's vertex cycle, :329-330; see
+ * DESIGN.md).  d_aux3[c] = {hull vertices, rectangle area, flag}:
+ *   hull vertices  the strict vertices of the exact convex hull of the xy points (collinear points and duplicates are none): 1 for
+ *                  identical points, 2 for collinear ones (ABI 1 wrote 0 for both), at most VG_BOX_MAX_HULL
+ *   flag 0                          the rectangle of smallest area over the edges of the whole hull
+ *   VG_BOX_FLAG_DEGENERATE (1)      fewer than 3 hull vertices (the reference: qhull raises, :320-326): the 0.1 m square at the float64
+ *                                   mean of the points, rz = 0, area 0
+ *   VG_BOX_FLAG_HULL_OVERFLOW (2)   more than VG_BOX_MAX_HULL hull vertices (a dense ring).  The wrapping stops there, with the part
+ *                                   of the outline that lies counter-clockwise from the lowest point, and NO rectangle is fitted:
+ *                                   cx, cy, l, w, rz = NaN, area 0, hull vertices = VG_BOX_MAX_HULL; cz and h are valid.  The caller
+ *                                   must fit that cluster itself (vilgod_amd/boxes.py all_edges_box; ABI 1 returned the
+ *                                   rectangle of the partial outline, flag 0). */
+#define VG_BOX_MAX_HULL 512
+#define VG_BOX_FLAG_DEGENERATE 1
+#define VG_BOX_FLAG_HULL_OVERFLOW 2
 int vg_cluster_boxes(const float* d_points, int stride, const int32_t* d_index, const int32_t* d_seg_off, int n_clusters,
                      double* d_box7, float* d_aux3, void* stream);
 

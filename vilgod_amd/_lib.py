@@ -80,6 +80,8 @@ FILTER_NAMES = ('filter_by_number_points', 'filter_by_height', 'filter_by_aspect
 FILTER_AND_REQUIRED, FILTER_AND, FILTER_OR = 0, 1, 2
 FILTER_NSTATS = 16
 FILTER_FLAG_DEGENERATE, FILTER_FLAG_HULL_OVERFLOW = 1, 2
+BOX_MAX_HULL = 512                                        # vg_cluster_boxes d_aux3 (VG_BOX_*)
+BOX_FLAG_DEGENERATE, BOX_FLAG_HULL_OVERFLOW = 1, 2
 
 
 class FilterParams(ctypes.Structure):

@@ -17,6 +17,8 @@ Two modes, selected by `PseudoLabelPipeline(box_mode=...)` / `device.box_mode`:
   'fast'      `vg_cluster_boxes` (csrc/segment.hip k_cluster_box): exact-predicate hull + rectangle over ALL hull edges in
               float64 on the GPU.  Identical to the reference whenever the best direction is not the dropped closing edge
               (~85 % of clusters), otherwise its rectangle is the smaller one.
+              A hull of more than 512 vertices exceeds the kernel's capacity: it reports that instead of a rectangle
+              (VG_BOX_FLAG_HULL_OVERFLOW) and `PseudoLabelPipeline.fit_boxes` fits that cluster here (`all_edges_box`).
 
 Host code is numpy because the reference's is; there is no CPU fallback for the GPU parts.
 """
@@ -26,16 +28,21 @@ from scipy import spatial
 PI2 = np.pi / 2.
 
 
-def minimum_bounding_rectangle(points):
+def minimum_bounding_rectangle(points, hull_points=None, all_edges=False):
     """pointcloud_utils.py:309-372, expression by expression (float32 in, float32 arithmetic like upstream).
+    hull_points / all_edges are this project's ('fast' mode's rule, `all_edges_box`): a hull cycle found elsewhere (>= 3 vertices; the
+    arithmetic takes its dtype) and the closing edge's direction as a candidate too.
     -> (corners (4,2) float64 array holding float32 values, rz, area)."""
-    try:
-        hull_points = points[spatial.ConvexHull(points).vertices]
-    except Exception:                                     # qhull raises on < 3 points / flat input (:320-326)
-        corners = np.ones((4, 2)) * np.mean(points[:, :2], axis=0)[:2]
-        corners += np.array([[-0.05, -0.05], [0.05, -0.05], [0.05, 0.05], [-0.05, 0.05]])
-        return corners, 0, 0
+    if hull_points is None:
+        try:
+            hull_points = points[spatial.ConvexHull(points).vertices]
+        except Exception:                                 # qhull raises on < 3 points / flat input (:320-326)
+            corners = np.ones((4, 2)) * np.mean(points[:, :2], axis=0)[:2]
+            corners += np.array([[-0.05, -0.05], [0.05, -0.05], [0.05, 0.05], [-0.05, 0.05]])
+            return corners, 0, 0
     edges = hull_points[1:] - hull_points[:-1]            # the closing edge of the vertex cycle is NOT there (:329-330)
+    if all_edges:
+        edges = np.vstack([edges, hull_points[:1] - hull_points[-1:]])
     angles = np.arctan2(edges[:, 1], edges[:, 0])
     angles = np.abs(np.mod(angles, PI2))
     angles = np.unique(angles)
@@ -68,6 +75,50 @@ def box_from_rectangle(corners, rz, zmin, zmax):
         rz += np.pi / 2
     height = zmax - zmin
     return np.array([c[0], c[1], zmin + height / 2, l, w, height + 0.3, rz])
+
+
+def exact_hull_xy(xy):
+    """Strict convex hull vertices (counter-clockwise, float64 [H,2]) of float32 xy points by a monotone chain on exact integers: what
+    k_cluster_box's gift wrapping with its exact orientation test finds, without its capacity.  Host fallback, rare: python speed."""
+    pts = sorted({(float(x), float(y)) for x, y in np.asarray(xy, dtype=np.float32)[:, :2]})
+    if len(pts) < 3:
+        return np.array(pts, dtype=np.float64).reshape(-1, 2)
+    den = max(max(x.as_integer_ratio()[1], y.as_integer_ratio()[1]) for x, y in pts)      # powers of two: one common scale
+
+    def ints(v):
+        n, d = v.as_integer_ratio()
+        return n * (den // d)
+    ip = [(ints(x), ints(y)) for x, y in pts]
+
+    def half(order):
+        h = []
+        for k in order:
+            while len(h) >= 2 and ((ip[h[-1]][0] - ip[h[-2]][0]) * (ip[k][1] - ip[h[-2]][1])
+                                   - (ip[h[-1]][1] - ip[h[-2]][1]) * (ip[k][0] - ip[h[-2]][0])) <= 0:
+                h.pop()
+            h.append(k)
+        return h[:-1]
+    idx = half(range(len(pts))) + half(range(len(pts) - 1, -1, -1))
+    return np.array([pts[k] for k in idx], dtype=np.float64)
+
+
+def all_edges_box(points):
+    """The box `vg_cluster_boxes` fits ('fast' mode: exact hull, every hull edge, float64; csrc/segment.hip k_cluster_box), computed on
+    the host for a cluster whose hull exceeds the kernel's capacity (VG_BOX_FLAG_HULL_OVERFLOW).  points: [n,>=3] float32.
+    -> [cx,cy,cz,l,w,h+0.3,rz] float64."""
+    points = np.asarray(points, dtype=np.float32)
+    z = points[:, 2]
+    zmin, zmax = z.min(), z.max()
+    height = np.float32(zmax - zmin)
+    cz, h = float(zmin) + float(height) / 2, float(height) + 0.3
+    hull = exact_hull_xy(points[:, :2])
+    if len(hull) < 3:
+        m = points[:, :2].astype(np.float64).mean(0)
+        return np.array([m[0], m[1], cz, 0.1, 0.1, h, 0.0])
+    corners, rz, _ = minimum_bounding_rectangle(None, hull, all_edges=True)      # (float64 hull: float64 arithmetic)
+    box = box_from_rectangle(corners, rz, 0.0, 0.0)
+    box[2], box[5] = cz, h
+    return box
 
 
 # ---- the method of fit_bounding_boxes_simple -----------------------------------------------------------------------------------

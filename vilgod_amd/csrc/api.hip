@@ -2,7 +2,7 @@
 #include "common.h"
 #include "vilgod_hip.h"
 
-extern "C" int vg_abi_version(void) { return 1; }
+extern "C" int vg_abi_version(void) { return 2; }
 
 // CU-masked streams (include/vilgod_hip.h, "execution resources")
 extern "C" int vg_stream_create_cu_mask(void** out_stream, const uint32_t* h_cu_mask, int n_words) {

@@ -169,13 +169,44 @@ __global__ __launch_bounds__(256) void k_cluster_filter(const float* __restrict_
 }
 
 // ---------------------------------------------------------------------------------------------
-#define BOX_MAX_HULL 512
-// exact sign of the orientation of (a,b,c) for float32 inputs: differences and their products are exact in float64
+#define BOX_MAX_HULL VG_BOX_MAX_HULL
+// Sign of the orientation of (a,b,c), exact for float32 inputs whose four differences are exact in float64: coordinates within 2^29
+// of each other in magnitude (any LiDAR cluster: 2^-20 m .. 2^9 m).  The two products need up to 2 x 53 bits, so their rounded
+// difference can have the wrong sign in a cluster that straddles an axis (coordinates from 2^-20 to 2^2 around a near-collinear
+// triple).  Where the rounded value is not safely away from zero, the products are split error-free (p + e = d1 * d2 with one fma)
+// and (p1 + e1) - (p2 + e2) is summed into a non-overlapping expansion (Shewchuk's Two-Two-Diff): its leading nonzero term has
+// the exact sign.  Only the sign and zero-ness of the result are meaningful.
+__device__ __forceinline__ void vg_two_sum(double a, double b, double& x, double& y) {
+    x = a + b;
+    const double bv = x - a, av = x - bv;
+    y = (a - av) + (b - bv);
+}
+__device__ __forceinline__ void vg_two_diff(double a, double b, double& x, double& y) {
+    x = a - b;
+    const double bv = a - x, av = x + bv;
+    y = (a - av) + (bv - b);
+}
+__device__ __noinline__ double vg_orient_exact(double d1, double d2, double d3, double d4, double p1, double p2) {
+    const double e1 = fma(d1, d2, -p1), e2 = fma(d3, d4, -p2);
+    double i, j, t, x0, x1, x2, x3;
+    vg_two_diff(e1, e2, i, x0);            // (p1, e1) - e2 -> (j, t, x0)
+    vg_two_sum(p1, i, j, t);
+    vg_two_diff(t, p2, i, x1);             // (j, t) - p2 -> (x3, x2, x1)
+    vg_two_sum(j, i, x3, x2);
+    return x3 != 0 ? x3 : x2 != 0 ? x2 : x1 != 0 ? x1 : x0;
+}
 __device__ __forceinline__ double vg_orient(double ax, double ay, double bx, double by, double cx, double cy) {
-    return (bx - ax) * (cy - ay) - (by - ay) * (cx - ax);
+    const double d1 = bx - ax, d2 = cy - ay, d3 = by - ay, d4 = cx - ax;
+    const double p1 = d1 * d2, p2 = d3 * d4;
+    const double det = p1 - p2;
+    // |det - exact| <= 2^-53 (|p1| + |p2|) + 2^-53 |p1 - p2|: beyond 2^-51 (|p1| + |p2|) the rounded sign is the exact one
+    if (fabs(det) > 0x1p-51 * (fabs(p1) + fabs(p2))) return det;
+    return vg_orient_exact(d1, d2, d3, d4, p1, p2);
 }
 
-// box[c] = {cx, cy, cz, l, w, h, rz} (float64, ref frame); aux[c] = {n_hull, area, degenerate}
+// box[c] = {cx, cy, cz, l, w, h, rz} (float64, ref frame); aux[c] = {n_hull, area, flag}: flag 0 = a rectangle over the whole hull,
+// VG_BOX_FLAG_DEGENERATE = fewer than 3 strict hull vertices (0.1 m square at the mean), VG_BOX_FLAG_HULL_OVERFLOW = the hull has
+// more than BOX_MAX_HULL vertices: NO rectangle is fitted (cx, cy, l, w, rz = NaN; cz, h valid), the caller fits that cluster itself
 __global__ __launch_bounds__(256) void k_cluster_box(const float* __restrict__ pts, int stride,
                                                      const int* __restrict__ index, const int* __restrict__ seg_off,
                                                      double* __restrict__ box, float* __restrict__ aux) {
@@ -234,10 +265,10 @@ __global__ __launch_bounds__(256) void k_cluster_box(const float* __restrict__ p
     zmin = red_z[0];
     zmax = red_z[4];
     // ---- gift wrapping (counter-clockwise): next = the point with no other point to its right; farthest on ties ----
-    bool degenerate = n < 3;
+    bool overflow = false;
     int hn = 0;                       // hull vertices so far: counted by every thread (uniform), so the loop exit never reads a
                                       // shared counter that thread 0 may already be advancing for the next iteration
-    while (!degenerate) {
+    while (n > 0) {
         const int cur = sh_cur;
         const double cx0 = PX(cur), cy0 = PY(cur);
         if (tid == 0 && hn < BOX_MAX_HULL) { hx[hn] = cx0; hy[hn] = cy0; }
@@ -283,28 +314,25 @@ __global__ __launch_bounds__(256) void k_cluster_box(const float* __restrict__ p
         }
         __syncthreads();
         const int nxt = sh_cur;
-        if (nxt < 0) { degenerate = true; break; }                       // all points coincide
+        if (nxt < 0) break;                                               // all points coincide: one vertex
         if (PX(nxt) == PX(sh_start) && PY(nxt) == PY(sh_start)) break;    // closed
-        if (hn >= BOX_MAX_HULL) break;                                   // safety (keeps a valid, coarser polygon)
+        // capacity: the vertices so far are the first BOX_MAX_HULL counter-clockwise from the lowest point, the rest of the outline is
+        // missing -- a rectangle over them would cover part of the object, so none is fitted
+        if (hn >= BOX_MAX_HULL) { overflow = true; break; }
     }
-    const int nh = degenerate ? 0 : min(hn, BOX_MAX_HULL);
-    // hull area (shoelace) to detect collinear input (qhull raises -> reference falls back to a 0.1 m square)
-    __shared__ double sh_area2;
-    if (tid == 0) {
-        double a2 = 0;
-        for (int i = 0; i < nh; ++i) {
-            int j = (i + 1) % nh;
-            a2 += hx[i] * hy[j] - hx[j] * hy[i];
-        }
-        sh_area2 = a2;
-    }
+    const int nh = hn;                                                    // strict hull vertices (<= BOX_MAX_HULL; 1 or 2: degenerate)
+    // fewer than 3 strict vertices = collinear or identical input (qhull raises -> the reference falls back to a 0.1 m square); three
+    // or more have area, the orientation test being exact
     __syncthreads();
     double out[7];
     float n_hull = (float)nh, area = 0.f, deg = 0.f;
     const float height = zmax - zmin;                                   // zero_shot_detector.py:459 (float32)
-    if (nh < 3 || !(fabs(sh_area2) > 0)) {
+    if (overflow) {
+        deg = (float)VG_BOX_FLAG_HULL_OVERFLOW;
+        out[0] = out[1] = out[3] = out[4] = out[6] = NAN;
+    } else if (nh < 3) {
         // pointcloud_utils.py:322-326: 0.1 m square at the mean, rz = 0
-        deg = 1.f;
+        deg = (float)VG_BOX_FLAG_DEGENERATE;
         double mx = sh_sum[0] / (double)n, my = sh_sum[1] / (double)n;
         out[0] = mx; out[1] = my; out[3] = 0.1; out[4] = 0.1; out[6] = 0.0;
         // corners (-.05,-.05),(.05,-.05),(.05,.05),(-.05,.05): l = |c0-c1| = 0.1, w = |c0-c3| = 0.1

@@ -25,7 +25,7 @@ import torch
 from scipy.spatial.transform import Rotation
 
 from ._lib import (lib, ptr, stream_ptr, check, FilterParams, FILTER_NAMES, FILTER_AND_REQUIRED, FILTER_AND, FILTER_OR, FILTER_NSTATS,
-                   FILTER_FLAG_HULL_OVERFLOW)
+                   FILTER_FLAG_HULL_OVERFLOW, BOX_FLAG_HULL_OVERFLOW)
 from .frame_state import (FrameState, pack_clusters, vote, static_from_entropy, pack_clusters_device, select_clusters_device,
                           PACK_MAX_LABEL_BOUND)
 from . import patchworkpp as gpw
@@ -668,7 +668,9 @@ class PseudoLabelPipeline:
 
     # [E1]
     def boxes(self, d_X, d_index, d_seg):
-        """'fast' mode kernel: exact hull + rectangle over ALL hull edges, float64 (csrc/segment.hip k_cluster_box)."""
+        """'fast' mode kernel: exact hull + rectangle over ALL hull edges, float64 (csrc/segment.hip k_cluster_box).
+        -> (CUDA [C,7] float64 boxes, CUDA [C,3] float32 aux: hull vertices, area, flag), as the kernel wrote them.  The caller MUST look
+        at aux[:, 2]: a row flagged BOX_FLAG_HULL_OVERFLOW holds NaN for cx, cy, l, w, rz, not a rectangle (`fit_boxes` refits it)."""
         C = d_seg.numel() - 1
         box = torch.empty((C, 7), dtype=torch.float64, device=self.device)
         aux = torch.empty((C, 3), dtype=torch.float32, device=self.device)
@@ -746,8 +748,21 @@ class PseudoLabelPipeline:
         if name != 'minimum_bounding_rectangle':
             return self.lshape_boxes(d_X, d_index, d_seg, name, args)[0].cpu().numpy()
         if self.box_mode == 'fast':
-            return self.boxes(d_X, d_index, d_seg)[0].cpu().numpy()
+            box, aux = self.boxes(d_X, d_index, d_seg)
+            box, aux = box.cpu().numpy(), aux.cpu().numpy()
+            over = np.flatnonzero(aux[:, 2] == BOX_FLAG_HULL_OVERFLOW)
+            if len(over):
+                # hulls beyond the kernel's LDS capacity (512 vertices; a dense ring): no rectangle came back, the host fits them
+                self._box_overflow(d_X, d_index, seg, over, box)
+            return box
         return self.fit_boxes_async(d_X, index, seg, d_index, d_seg, xy_host, zmin, zmax).result()
+
+    def _box_overflow(self, d_X, d_index, seg, rows, box):
+        """Host refit of the clusters `rows`; their points are gathered through the device's list (pack='device' keeps none on the host)."""
+        from .boxes import all_edges_box
+        for c in rows:
+            rows_c = d_index[int(seg[c]):int(seg[c + 1])].long()
+            box[c] = all_edges_box(d_X[rows_c, :3].cpu().numpy())
 
     def fit_boxes_async(self, d_X, index, seg, d_index=None, d_seg=None, xy_host=None, zmin=None, zmax=None):
         """Reference mode: start the host part (vilgod_amd/boxes.py) in a helper process; .result() -> [C,7] boxes."""
