@@ -67,6 +67,27 @@ int vg_to_origin(const float* d_ego, const int32_t* d_point_cluster, int n, cons
 int vg_render_crops(const float* d_origin, const int32_t* d_seg_off, int n_clusters, const float* d_view_rot,
                     int n_views, const float* d_lut, void* d_out, int out_kind, void* stream);
 
+/* vg_render_crops at any `lidar_image_projection` setting (tools/configs/preprocessor/waymo.yaml:75-80; src/utils/mv_utils.py:91-127
+ * points2grid takes the four numbers from the config, :158-161).  vg_render_crops is the shipped setting (112, 8, 0.8, 0.2) with the
+ * numbers compiled in; this entry point runs a second kernel that takes them as arguments and computes the same chain:
+ *   resolution    16 .. 128: grid side; the image is (resolution - 2)^2, resized to 224 with scale float(resolution - 3) / 223
+ *   depth         3 .. 32: depth slices; values are clipped to 1 .. depth - 2, the slice is the unclipped ceil (mv_utils.py:114-118)
+ *   obj_ratio     (0, 1], depth_bias [0, 1]: float32, as torch rounds the Python scalars
+ *   one_plus_bias float32( 1.0 + (double)depth_bias_as_configured ): torch forms `1 + depth_bias` (mv_utils.py:110) in double before
+ *                 it meets the float32 tensor, so the caller does too (1 <= one_plus_bias <= 2)
+ * out_kind as above, kind 3 is [n, resolution - 2, resolution - 2]; the output side stays 224.  VG_ERR_ARG (nothing launched) for a
+ * null `params` or any value outside these ranges, also when there is nothing to render. */
+#define VG_RENDER_MIN_RESOLUTION 16
+#define VG_RENDER_MAX_RESOLUTION 128
+#define VG_RENDER_MIN_DEPTH 3
+#define VG_RENDER_MAX_DEPTH 32
+typedef struct vg_render_params {
+    int resolution, depth;
+    float obj_ratio, depth_bias, one_plus_bias;
+} vg_render_params;
+int vg_render_crops_ex(const float* d_origin, const int32_t* d_seg_off, int n_clusters, const float* d_view_rot, int n_views,
+                       const float* d_lut, const vg_render_params* params, void* d_out, int out_kind, void* stream);
+
 /* ---- CLIP ViT image tower + zero-shot scores (rows D7, D9) --------------------------------------
  * Replaces ClipWrapper.predict_clip_labels' GPU part, src/utils/clip_utils.py:37-44:
  *   model.encode_image (third_party/CLIP/clip/model.py:340-341 -> VisionTransformer.forward :223-240,

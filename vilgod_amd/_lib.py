@@ -103,6 +103,20 @@ class FilterParams(ctypes.Structure):
         lib.vg_filter_default_params(ctypes.byref(self))
 
 
+class RenderParams(ctypes.Structure):
+    """vg_render_params (include/vilgod_hip.h), passed by reference to vg_render_crops_ex.  `one_plus_bias` is 1 + depth_bias formed in
+    double and rounded to float32, which is what torch does with the Python scalar at mv_utils.py:110."""
+    _fields_ = [('resolution', ctypes.c_int), ('depth', ctypes.c_int),
+                ('obj_ratio', ctypes.c_float), ('depth_bias', ctypes.c_float), ('one_plus_bias', ctypes.c_float)]
+
+    def __init__(self, resolution=112, depth=8, obj_ratio=0.8, depth_bias=0.2):
+        super().__init__(int(resolution), int(depth), float(obj_ratio), float(depth_bias), 1.0 + float(depth_bias))
+
+
+RENDER_RESOLUTION = tuple(int(re.search(rf'#define\s+VG_RENDER_{k}_RESOLUTION\s+(\d+)', open(HEADER).read()).group(1)) for k in ('MIN', 'MAX'))
+RENDER_DEPTH = tuple(int(re.search(rf'#define\s+VG_RENDER_{k}_DEPTH\s+(\d+)', open(HEADER).read()).group(1)) for k in ('MIN', 'MAX'))
+
+
 def ptr(t):
     """Device/host pointer of a torch tensor (or None)."""
     if t is None:

@@ -13,12 +13,15 @@
 //   k_render          D2-D6: one 1024-thread workgroup per (cluster, view); the 112x112 depth
 //                     slice, the 5x5 max-pool, the 3x3 Gaussian and the 110x110 image live in
 //                     LDS (~100 KB of the CU's 160 KB); only the final 224x224 crop is written.
+//   k_render_ex       k_render with resolution, depth, obj_ratio and depth_bias as arguments (vg_render_crops_ex); k_render keeps
+//                     the shipped setting compiled in and is what the default path launches.
 //
 // Arithmetic follows torch-CPU float32 op for op (orders established empirically against the
 // reference run on CPU, see DESIGN.md "renderer numerics"): matmul and 3x3 conv are FMA chains,
 // bilinear is fma(a,wa,b*wb).  This file is compiled with -ffp-contract=off so that only the
 // FMAs written below exist.
 #include "common.h"
+#include "vilgod_hip.h"
 #include <hip/hip_fp16.h>
 
 #define GR 112           // grid resolution (waymo.yaml: resolution)
@@ -558,6 +561,376 @@ __global__ __launch_bounds__(RT) void k_render(RenderArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// k_render_ex: k_render with the four `lidar_image_projection` numbers as arguments (mv_utils.py:91-127, 158-161).
+//   resolution R (16..128): grid side R, image side R - 2, clip bounds 1 .. R - 2, interpolation scale float(R - 3) / 223
+//   depth D (3..32): slices 0 .. D - 1 in ONE 32-bit occupancy word, value clipped to 1 .. D - 2, slice = the unclipped ceil
+//   obj_ratio, depth_bias and 1 + depth_bias as float32 (the sum is formed in double by the caller, like torch does with the Python
+//   scalar); the float32 operation order of points2grid is kept: true divisions, nothing contracted.
+// LDS: S = [R][R] at float 0, T = [R][R-2] at float `t_off`.  t_off = R * R, except for the patch-row kinds at R < 112: they stage the
+// 224 x 224 uint8 image (50 176 bytes) at byte 0 while the bilinear pass still reads the image in T, so T then starts behind it.
+// MAXACC = accumulators per thread = ceil((R-2)^2 / 1024) at the largest R of the instantiation (12: R <= 112, 16: R <= 128); the bound
+// is compile-time so that the running maxima stay in registers.
+struct RenderExParams {
+    int R, D;
+    int t_off;              // float offset of T inside the dynamic LDS
+    float ratio, bias, one_plus_bias;
+};
+
+__device__ __forceinline__ void quantise_point_ex(float px, float py, float pz, const float* pc, float prange, float ratio, float bias,
+                                                  float opb, float Rf, float xy_hi, float Dm2, int& gx, int& gy, int& gz, float& val) {
+    // mv_utils.py:105-118, float32 op for op
+    float nx = (px - pc[0]) / prange * 2.0f;
+    float ny = (py - pc[1]) / prange * 2.0f;
+    float nz = (pz - pc[2]) / prange * 2.0f;
+    nx = nx * ratio;
+    ny = ny * ratio;
+    float fx = ceilf((nx + 1.0f) / 2.0f * Rf);
+    float fy = ceilf((ny + 1.0f) / 2.0f * Rf);
+    float fz = ((nz + 1.0f) / 2.0f + bias) / opb * Dm2;
+    float zi = ceilf(fz);
+    fx = fminf(fmaxf(fx, 1.0f), xy_hi);
+    fy = fminf(fmaxf(fy, 1.0f), xy_hi);
+    val = fminf(fmaxf(fz, 1.0f), Dm2);
+    gx = (int)fx;
+    gy = (int)fy;
+    gz = (int)zi;
+}
+
+template <int MAXACC>
+__global__ __launch_bounds__(RT) void k_render_ex(RenderArgs a, RenderExParams p) {
+    extern __shared__ float lds[];
+    const int R = p.R, G = p.R - 2, D = p.D;     // grid side, image side, slices
+    float* S = lds;                  // [R][R] depth slice, later [G][G] pooled (row stride R)
+    float* T = lds + p.t_off;        // [R][G] row-pooled, later [G][G] final image
+    __shared__ float red[16 * 6];
+    __shared__ float bc[8];          // pcent[3], prange, image max
+    __shared__ unsigned int slice_mask;
+    __shared__ int t_i0[OUT];
+    __shared__ float t_l0[OUT], t_l1[OUT];
+    __shared__ int s_cluster;
+    __shared__ int bb[4];            // r0, r1, c0, c1 of the current slice
+
+    const int tid = threadIdx.x;
+    const int V = a.n_views;
+    // largest clusters first, as in k_render
+    {
+        const int C = a.n_clusters, want = (int)blockIdx.x / V;
+        if (C > 1024) { if (tid == 0) s_cluster = want; }
+        else
+        for (int t = tid; t < C; t += RT) {
+            const int sz = a.seg_off[t + 1] - a.seg_off[t];
+            int rank = 0;
+            for (int u = 0; u < C; ++u) {
+                const int su = a.seg_off[u + 1] - a.seg_off[u];
+                rank += (su > sz || (su == sz && u < t)) ? 1 : 0;
+            }
+            if (rank == want) s_cluster = t;
+        }
+        __syncthreads();
+    }
+    const int c = s_cluster, v = blockIdx.x % V;
+    const int crop_id = c * V + v;
+    const int p0 = a.seg_off[c], P = a.seg_off[c + 1] - p0;
+    const float* pts = a.origin + (size_t)p0 * 3;
+    float r[9];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) r[i] = a.view_rot[v * 9 + i];
+    const float ratio = p.ratio, bias = p.bias, opb = p.one_plus_bias;
+    const float Rf = (float)R, xy_hi = (float)(R - 2), Dm2 = (float)(D - 2);
+
+    if (tid == 0) slice_mask = 0u;
+    if (tid < OUT) {
+        // F.interpolate(..., align_corners=True): src = ((R - 3) / 223) * dst in float32
+        float scale = (float)(R - 3) / 223.0f;
+        float src = scale * (float)tid;
+        int i0 = (int)src;
+        if (i0 > G - 1) i0 = G - 1;
+        float l1 = src - (float)i0;
+        t_i0[tid] = i0;
+        t_l1[tid] = l1;
+        t_l0[tid] = 1.0f - l1;
+    }
+
+    // ---- per-view bounding box (mv_utils.py:101-104) ----------------------------------------
+    float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (int i = tid; i < P; i += RT) {
+        float x = pts[i * 3 + 0], y = pts[i * 3 + 1], z = pts[i * 3 + 2];
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            float pv = fmaf(z, r[6 + j], fmaf(y, r[3 + j], x * r[j]));
+            mn[j] = fminf(mn[j], pv);
+            mx[j] = fmaxf(mx[j], pv);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        mn[j] = vg_wave_min(mn[j]);
+        mx[j] = vg_wave_max(mx[j]);
+    }
+    const int wid = tid >> 6, lane = tid & 63;
+    if (lane == 0) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            red[wid * 6 + j] = mn[j];
+            red[wid * 6 + 3 + j] = mx[j];
+        }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+        for (int w = 0; w < RT / 64; ++w)
+            for (int j = 0; j < 3; ++j) {
+                lo[j] = fminf(lo[j], red[w * 6 + j]);
+                hi[j] = fmaxf(hi[j], red[w * 6 + 3 + j]);
+            }
+        float pr = -INFINITY;
+        for (int j = 0; j < 3; ++j) {
+            bc[j] = (hi[j] + lo[j]) / 2.0f;
+            pr = fmaxf(pr, hi[j] - lo[j]);
+        }
+        bc[3] = pr;
+    }
+    __syncthreads();
+    const float pc[3] = {bc[0], bc[1], bc[2]};
+    const float prange = bc[3];
+
+    // which depth slices are occupied at all?  (D <= 32: one word)
+    unsigned int mymask = 0u;
+    for (int i = tid; i < P; i += RT) {
+        float x = pts[i * 3 + 0], y = pts[i * 3 + 1], z = pts[i * 3 + 2];
+        float pv0 = fmaf(z, r[6], fmaf(y, r[3], x * r[0]));
+        float pv1 = fmaf(z, r[7], fmaf(y, r[4], x * r[1]));
+        float pv2 = fmaf(z, r[8], fmaf(y, r[5], x * r[2]));
+        int gx, gy, gz;
+        float val;
+        quantise_point_ex(pv0, pv1, pv2, pc, prange, ratio, bias, opb, Rf, xy_hi, Dm2, gx, gy, gz, val);
+        if (gz >= 0 && gz < D) mymask |= 1u << gz;
+    }
+    if (mymask) atomicOr(&slice_mask, mymask);
+    __syncthreads();
+    const unsigned int smask = slice_mask;
+
+    float acc[MAXACC];
+#pragma unroll
+    for (int k = 0; k < MAXACC; ++k) acc[k] = 0.0f;
+    const float g_c = a.lut[768 + 0], g_e = a.lut[768 + 1], g_m = a.lut[768 + 2];  // corner, edge, middle
+
+    // per slice only the footprint of its points is processed: the ranges of k_render with 112 -> R, 110 -> G
+    for (int d = 0; d < D; ++d) {
+        if (!((smask >> d) & 1u)) continue;   // empty slice: pool/conv give 0, acc >= 0 already
+        for (int i = tid; i < R * R; i += RT) S[i] = 0.0f;
+        if (tid == 0) { bb[0] = R; bb[1] = -1; bb[2] = R; bb[3] = -1; }
+        __syncthreads();
+        int r0 = R, r1 = -1, c0 = R, c1 = -1;
+        for (int i = tid; i < P; i += RT) {
+            float x = pts[i * 3 + 0], y = pts[i * 3 + 1], z = pts[i * 3 + 2];
+            float pv0 = fmaf(z, r[6], fmaf(y, r[3], x * r[0]));
+            float pv1 = fmaf(z, r[7], fmaf(y, r[4], x * r[1]));
+            float pv2 = fmaf(z, r[8], fmaf(y, r[5], x * r[2]));
+            int gx, gy, gz;
+            float val;
+            quantise_point_ex(pv0, pv1, pv2, pc, prange, ratio, bias, opb, Rf, xy_hi, Dm2, gx, gy, gz, val);
+            // grid[z][y][x] then permute(0,1,3,2): image row = x, column = y (mv_utils.py:120-125); gx, gy in [1, R - 2]
+            if (gz == d) {
+                atomicMax((int*)&S[gx * R + gy], __float_as_int(val));
+                r0 = min(r0, gx); r1 = max(r1, gx); c0 = min(c0, gy); c1 = max(c1, gy);
+            }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            r0 = min(r0, __shfl_xor(r0, o)); r1 = max(r1, __shfl_xor(r1, o));
+            c0 = min(c0, __shfl_xor(c0, o)); c1 = max(c1, __shfl_xor(c1, o));
+        }
+        if (lane == 0 && r1 >= 0) { atomicMin(&bb[0], r0); atomicMax(&bb[1], r1); atomicMin(&bb[2], c0); atomicMax(&bb[3], c1); }
+        __syncthreads();
+        r0 = bb[0]; r1 = bb[1]; c0 = bb[2]; c1 = bb[3];
+        const int tj0 = max(c0 - 3, 0), tj1 = min(c1 + 1, G - 1), tw = tj1 - tj0 + 1;          // columns of T and of the pooled image
+        const int ti0 = max(r0 - 4, 0), ti1 = min(r1 + 4, R - 1);                                // rows of T
+        // MaxPool3d (1,5,5) pad (0,1,1): window [i-1, i+3] x [j-1, j+3]; separable.  j <= G - 1 = R - 3: j + 2 <= R - 1 is inside the row
+        for (int q = tid; q < (ti1 - ti0 + 1) * tw; q += RT) {
+            const int di = q / tw;
+            const int i = ti0 + di, j = tj0 + (q - di * tw);
+            const float* row = S + i * R;
+            float m = row[j];
+            if (j >= 1) m = fmaxf(m, row[j - 1]);
+            m = fmaxf(m, row[j + 1]);
+            m = fmaxf(m, row[j + 2]);
+            if (j + 3 < R) m = fmaxf(m, row[j + 3]);
+            T[i * G + j] = m;
+        }
+        __syncthreads();
+        const int pi0 = max(r0 - 3, 0), pi1 = min(r1 + 1, G - 1);                                // rows of the pooled image; i + 2 <= R - 1
+        for (int q = tid; q < (pi1 - pi0 + 1) * tw; q += RT) {
+            const int di = q / tw;
+            const int i = pi0 + di, j = tj0 + (q - di * tw);
+            float m = T[i * G + j];
+            if (i >= 1) m = fmaxf(m, T[(i - 1) * G + j]);
+            m = fmaxf(m, T[(i + 1) * G + j]);
+            m = fmaxf(m, T[(i + 2) * G + j]);
+            if (i + 3 < R) m = fmaxf(m, T[(i + 3) * G + j]);
+            S[i * R + j] = m;   // pooled, raw row stride
+        }
+        __syncthreads();
+        // Conv3d (1,3,3) zero pad, FMA chain in row-major tap order; running max over depth.  The thread id is made opaque per slice
+        // for the reason given in k_render (hoisted per-pixel terms spill).
+        int tq = tid;
+        asm volatile("" : "+v"(tq));
+        const int ci0 = max(r0 - 4, 0), ci1 = min(r1 + 2, G - 1), cj0 = max(c0 - 4, 0), cj1 = min(c1 + 2, G - 1);
+#pragma unroll
+        for (int k = 0; k < MAXACC; ++k) {
+            int q = tq + k * RT;
+            if (q < G * G) {
+                int i = q / G, j = q - i * G;
+                if (i < ci0 || i > ci1 || j < cj0 || j > cj1) continue;      // the dense pass gives exactly 0 here
+                float s[9];
+#pragma unroll
+                for (int di = 0; di < 3; ++di)
+#pragma unroll
+                    for (int dj = 0; dj < 3; ++dj) {
+                        int ii = i + di - 1, jj = j + dj - 1;
+                        s[di * 3 + dj] = (ii >= 0 && ii < G && jj >= 0 && jj < G) ? S[ii * R + jj] : 0.0f;
+                    }
+                float o = s[0] * g_c;
+                o = fmaf(s[1], g_e, o);
+                o = fmaf(s[2], g_c, o);
+                o = fmaf(s[3], g_e, o);
+                o = fmaf(s[4], g_m, o);
+                o = fmaf(s[5], g_e, o);
+                o = fmaf(s[6], g_c, o);
+                o = fmaf(s[7], g_e, o);
+                o = fmaf(s[8], g_c, o);
+                acc[k] = fmaxf(acc[k], o);
+            }
+        }
+        __syncthreads();
+    }
+
+    // ---- normalise: img = 1 - img / max(img)  (mv_utils.py:34-35) ---------------------------
+    float m = 0.0f;
+#pragma unroll
+    for (int k = 0; k < MAXACC; ++k) m = fmaxf(m, acc[k]);
+    m = vg_wave_max(m);
+    if (lane == 0) red[wid] = m;
+    __syncthreads();
+    if (tid == 0) {
+        float mm = 0.0f;
+        for (int w = 0; w < RT / 64; ++w) mm = fmaxf(mm, red[w]);
+        bc[4] = mm;
+    }
+    __syncthreads();
+    const float imax = bc[4];
+#pragma unroll
+    for (int k = 0; k < MAXACC; ++k) {
+        int q = tid + k * RT;
+        if (q < G * G) T[q] = 1.0f - acc[k] / imax;
+    }
+    __syncthreads();
+    if (a.out_kind == 3) {   // raw get_img() image, one channel: f32 [n,R-2,R-2]
+        float* of = (float*)a.out + (size_t)crop_id * G * G;
+        for (int q = tid; q < G * G; q += RT) of[q] = T[q];
+        return;
+    }
+
+    // ---- D5 + D6: bilinear (R-2) -> 224, H<->W swap, uint8 truncation, CLIP normalise -------
+    const size_t crop = (size_t)crop_id;
+    for (int q4 = tid; q4 < OUT * OUT / 4; q4 += RT) {
+        int i = q4 / (OUT / 4);
+        int j0 = (q4 - i * (OUT / 4)) * 4;
+        int w0 = t_i0[i];
+        int w1 = w0 + (w0 < G - 1 ? 1 : 0);
+        float lw0 = t_l0[i], lw1 = t_l1[i];
+        unsigned char u[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            int j = j0 + e;
+            int h0 = t_i0[j];
+            int h1 = h0 + (h0 < G - 1 ? 1 : 0);
+            float lh0 = t_l0[j], lh1 = t_l1[j];
+            float p00 = T[h0 * G + w0], p01 = T[h0 * G + w1];
+            float p10 = T[h1 * G + w0], p11 = T[h1 * G + w1];
+            float t0 = fmaf(p00, lw0, p01 * lw1);
+            float t1 = fmaf(p10, lw0, p11 * lw1);
+            float o = fmaf(t0, lh0, t1 * lh1);
+            float s255 = o * 255.0f;
+            int iv = (int)s255;              // np.uint8(): truncation
+            iv = iv < 0 ? 0 : (iv > 255 ? 255 : iv);
+            u[e] = (unsigned char)iv;
+        }
+        if (a.out_kind >= 4) {
+            // patch rows: stage the quantised image at byte 0 of the LDS (row stride 224 bytes, whatever R is: 4-byte aligned); T lies
+            // behind the 50 176 staged bytes (t_off)
+            *(unsigned int*)((unsigned char*)S + i * OUT + j0) = (unsigned int)u[0] | ((unsigned int)u[1] << 8) | ((unsigned int)u[2] << 16) |
+                                                                 ((unsigned int)u[3] << 24);
+        } else if (a.out_kind == 0) {
+            unsigned char* o8 = (unsigned char*)a.out + (crop * OUT * OUT + (size_t)i * OUT + j0) * 3;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                o8[e * 3 + 0] = u[e];
+                o8[e * 3 + 1] = u[e];
+                o8[e * 3 + 2] = u[e];
+            }
+        } else if (a.out_kind == 1) {
+            float* of = (float*)a.out + crop * 3 * OUT * OUT + (size_t)i * OUT + j0;
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) {
+                float4 f4 = make_float4(a.lut[ch * 256 + u[0]], a.lut[ch * 256 + u[1]], a.lut[ch * 256 + u[2]],
+                                        a.lut[ch * 256 + u[3]]);
+                *(float4*)(of + (size_t)ch * OUT * OUT) = f4;
+            }
+        } else {
+            __half* oh = (__half*)a.out + crop * 3 * OUT * OUT + (size_t)i * OUT + j0;
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) {
+                __half2 h01 = __floats2half2_rn(a.lut[ch * 256 + u[0]], a.lut[ch * 256 + u[1]]);
+                __half2 h23 = __floats2half2_rn(a.lut[ch * 256 + u[2]], a.lut[ch * 256 + u[3]]);
+                uint2 pk;
+                pk.x = *(unsigned int*)&h01;
+                pk.y = *(unsigned int*)&h23;
+                *(uint2*)(oh + (size_t)ch * OUT * OUT) = pk;
+            }
+        }
+    }
+    if (a.out_kind == 4) {
+        // fp16 patch rows, enumerated in output order (see k_render)
+        __syncthreads();
+        const unsigned char* U = (const unsigned char*)S;
+        __half* ob = (__half*)a.out + crop * 196 * 768;
+        for (int q = tid; q < 196 * 192; q += RT) {
+            const int pp = q / 192, rem = q - pp * 192;
+            const int ch = rem >> 6, pi = (rem >> 2) & 15, pj4 = rem & 3;
+            const int py = pp / 14, px = pp - py * 14;
+            const unsigned int u4 = *(const unsigned int*)(U + (py * 16 + pi) * OUT + px * 16 + pj4 * 4);
+            const float* lut = a.lut + ch * 256;
+            __half2 h01 = __floats2half2_rn(lut[u4 & 255u], lut[(u4 >> 8) & 255u]);
+            __half2 h23 = __floats2half2_rn(lut[(u4 >> 16) & 255u], lut[u4 >> 24]);
+            uint2 pk;
+            pk.x = *(unsigned int*)&h01;
+            pk.y = *(unsigned int*)&h23;
+            *(uint2*)(ob + (size_t)pp * 768 + rem * 4) = pk;
+        }
+    }
+    if (a.out_kind == 5) {
+        // single-channel patch rows (see k_render)
+        __syncthreads();
+        const unsigned char* U = (const unsigned char*)S;
+        __half* ob = (__half*)a.out + crop * 196 * 256;
+        for (int q = tid; q < 196 * 64; q += RT) {
+            const int pp = q >> 6, rem = q & 63;
+            const int pi = rem >> 2, pj4 = rem & 3;
+            const int py = pp / 14, px = pp - py * 14;
+            const unsigned int u4 = *(const unsigned int*)(U + (py * 16 + pi) * OUT + px * 16 + pj4 * 4);
+            const float sc = 0.00390625f;                               // 2^-8: level / 256 is exact in fp16
+            __half2 h01 = __floats2half2_rn((float)(u4 & 255u) * sc, (float)((u4 >> 8) & 255u) * sc);
+            __half2 h23 = __floats2half2_rn((float)((u4 >> 16) & 255u) * sc, (float)(u4 >> 24) * sc);
+            uint2 pk;
+            pk.x = *(unsigned int*)&h01;
+            pk.y = *(unsigned int*)&h23;
+            *(uint2*)(ob + (size_t)pp * 256 + rem * 4) = pk;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 extern "C" {
 
 int vg_gather_ego(const float* d_points, int stride, const int32_t* d_index, int n, const double* d_T4x4,
@@ -615,6 +988,47 @@ int vg_render_crops(const float* d_origin, const int32_t* d_seg_off, int n_clust
     a.n_clusters = n_clusters;
     a.out_kind = out_kind;
     hipLaunchKernelGGL(k_render, dim3(n_clusters * n_views), dim3(RT), lds_bytes, (hipStream_t)stream, a);
+    VG_LAUNCH_CHECK();
+    return VG_OK;
+}
+
+int vg_render_crops_ex(const float* d_origin, const int32_t* d_seg_off, int n_clusters, const float* d_view_rot, int n_views,
+                       const float* d_lut, const vg_render_params* params, void* d_out, int out_kind, void* stream) {
+    // the parameters are validated before anything else: a bad setting is an error for an empty frame too
+    if (!params) return VG_ERR_ARG;
+    const int R = params->resolution, D = params->depth;
+    if (R < VG_RENDER_MIN_RESOLUTION || R > VG_RENDER_MAX_RESOLUTION || D < VG_RENDER_MIN_DEPTH || D > VG_RENDER_MAX_DEPTH) return VG_ERR_ARG;
+    if (!(params->obj_ratio > 0.0f && params->obj_ratio <= 1.0f) || !(params->depth_bias >= 0.0f && params->depth_bias <= 1.0f) ||
+        !(params->one_plus_bias >= 1.0f && params->one_plus_bias <= 2.0f))
+        return VG_ERR_ARG;
+    if (n_clusters <= 0 || n_views <= 0) return VG_OK;
+    if (!d_origin || !d_seg_off || !d_view_rot || !d_lut || !d_out || out_kind < 0 || out_kind > 5) return VG_ERR_ARG;
+    RenderExParams p;
+    p.R = R;
+    p.D = D;
+    // the patch-row kinds stage 224 x 224 bytes in front of T (k_render_ex)
+    p.t_off = (out_kind >= 4 && R * R < OUT * OUT / 4) ? OUT * OUT / 4 : R * R;
+    p.ratio = params->obj_ratio;
+    p.bias = params->depth_bias;
+    p.one_plus_bias = params->one_plus_bias;
+    const size_t lds_bytes = (size_t)(p.t_off + R * (R - 2)) * sizeof(float);
+    const size_t lds_max = (size_t)(VG_RENDER_MAX_RESOLUTION * VG_RENDER_MAX_RESOLUTION + VG_RENDER_MAX_RESOLUTION * (VG_RENDER_MAX_RESOLUTION - 2)) * sizeof(float);
+    RenderArgs a;
+    a.origin = d_origin;
+    a.seg_off = d_seg_off;
+    a.view_rot = d_view_rot;
+    a.lut = d_lut;
+    a.out = d_out;
+    a.n_views = n_views;
+    a.n_clusters = n_clusters;
+    a.out_kind = out_kind;
+    if (R <= GR) {
+        VG_MAX_DYNAMIC_LDS(k_render_ex<12>, lds_max);
+        hipLaunchKernelGGL(k_render_ex<12>, dim3(n_clusters * n_views), dim3(RT), lds_bytes, (hipStream_t)stream, a, p);
+    } else {
+        VG_MAX_DYNAMIC_LDS(k_render_ex<16>, lds_max);
+        hipLaunchKernelGGL(k_render_ex<16>, dim3(n_clusters * n_views), dim3(RT), lds_bytes, (hipStream_t)stream, a, p);
+    }
     VG_LAUNCH_CHECK();
     return VG_OK;
 }

@@ -7,6 +7,7 @@ HIP kernels of csrc/render.hip and returns the ViT-ready crops without leaving t
 keeps the reference's per-call interface for parity tests.
 """
 import contextlib
+import ctypes
 
 import numpy as np
 import torch
@@ -48,6 +49,44 @@ def _gaussian_taps(sigma):
     return float(k2[0, 0]), float(k2[0, 1]), float(k2[1, 1])
 
 
+def _as_tuple(v):
+    """kernel_size / stride / padding of a 3-d torch layer as torch reads it: one int stands for all three axes"""
+    return (int(v),) * 3 if isinstance(v, (int, np.integer)) else tuple(int(x) for x in v)
+
+
+def _check_cfg(get, resolution, depth, obj_ratio, depth_bias):
+    """What csrc/render.hip renders: the four numbers inside the ranges of vg_render_crops_ex, the grid-to-image geometry of the shipped
+    configs.  Anything else is refused by name (no silent approximation of a setting the kernels do not compute)."""
+    def refuse(key, value, want):
+        raise NotImplementedError(f'lidar_image_projection.{key} = {value!r}: csrc/render.hip renders {want}')
+
+    def integral(v):
+        return isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+
+    def real(v):
+        return isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool)
+    (r0, r1), (d0, d1) = _lib.RENDER_RESOLUTION, _lib.RENDER_DEPTH
+    if not integral(resolution) or not r0 <= resolution <= r1:
+        refuse('resolution', resolution, f'integers {r0} .. {r1}')
+    if not integral(depth) or not d0 <= depth <= d1:
+        refuse('depth', depth, f'integers {d0} .. {d1}')
+    if not real(obj_ratio) or not 0.0 < obj_ratio <= 1.0:
+        refuse('obj_ratio', obj_ratio, 'values in (0, 1]')
+    if not real(depth_bias) or not 0.0 <= depth_bias <= 1.0:
+        refuse('depth_bias', depth_bias, 'values in [0, 1]')
+    bg = get('bg_clr', 0.0)
+    if bg is not None and float(bg) != 0.0:
+        refuse('bg_clr', bg, 'an empty grid of zeros only (0.0)')
+    for key, kernel in (('maxpool', (1, 5, 5)), ('conv3d', (1, 3, 3))):
+        layer = get(key)
+        if layer is None:
+            continue
+        lget = layer.get if hasattr(layer, 'get') else (lambda k, d=None, _l=layer: getattr(_l, k, d))
+        got = (_as_tuple(lget('kernel_size', kernel)), _as_tuple(lget('stride', 1)), _as_tuple(lget('padding', (0, 1, 1))))
+        if got != (kernel, (1, 1, 1), (0, 1, 1)):
+            refuse(key, dict(kernel_size=got[0], stride=got[1], padding=got[2]), f'kernel_size {kernel}, stride 1, padding (0, 1, 1) only')
+
+
 class RealisticProjection:
     def __init__(self, lidar_image_projection_cfg, device='cuda', views=None, angle_mode='device'):
         cfg = lidar_image_projection_cfg
@@ -56,9 +95,13 @@ class RealisticProjection:
         self.depth = get('depth', 8)
         self.obj_ratio = get('obj_ratio', 0.8)
         self.depth_bias = get('depth_bias', 0.2)
+        _check_cfg(get, self.resolution, self.depth, self.obj_ratio, self.depth_bias)
+        self.image_side = int(self.resolution) - 2                                    # get_img's H = W (max-pool: R + 2 - 5 + 1)
+        # the shipped setting runs k_render, which has the four numbers compiled in (vg_render_crops); any other setting runs the
+        # parameterised kernel (vg_render_crops_ex) -- the same chain, the numbers as arguments
+        self._params = None
         if (self.resolution, self.depth, self.obj_ratio, self.depth_bias) != (112, 8, 0.8, 0.2):
-            raise NotImplementedError('csrc/render.hip is specialised for resolution 112, depth 8, obj_ratio 0.8, '
-                                      'depth_bias 0.2 (tools/configs/preprocessor/*.yaml)')
+            self._params = _lib.RenderParams(self.resolution, self.depth, self.obj_ratio, self.depth_bias)
         gk = get('gaussian_kernel', {'sigma': 3, 'zsigma': 1})
         sigma = gk['sigma'] if isinstance(gk, dict) else gk.sigma
         views = VIEWS_4 if views is None else views
@@ -116,7 +159,7 @@ class RealisticProjection:
                 result = torch.empty((rows, width), dtype=torch.float16, device=dev)
                 result[n * 196:].zero_()
         else:
-            result = torch.empty((n, 110, 110), dtype=torch.float32, device=dev)
+            result = torch.empty((n, self.image_side, self.image_side), dtype=torch.float32, device=dev)
         if n_clusters == 0 or ptot == 0:
             return result
         sp = stream_ptr(stream)
@@ -137,8 +180,7 @@ class RealisticProjection:
         origin = torch.empty((ptot, 3), dtype=torch.float32, device=dev)
         check(lib.vg_to_origin(ptr(ego), ptr(pt_cluster), ptot, ptr(med), ptr(rot), ptr(self._d_timg), ptr(origin), sp),
               'vg_to_origin')
-        check(lib.vg_render_crops(ptr(origin), ptr(seg_off), n_clusters, ptr(self._d_rot), V, ptr(self._d_lut),
-                                  ptr(result), kind, sp), 'vg_render_crops')
+        self._render(origin, seg_off, n_clusters, result, kind, sp)
         self._last = dict(ego=ego, median=med, origin=origin, rot=rot)
         return result
 
@@ -147,18 +189,25 @@ class RealisticProjection:
         kind = {'u8': OUT_U8, 'f32': OUT_F32, 'f16': OUT_F16, 'raw110': OUT_RAW110}[out]
         n = (seg_off.numel() - 1) * self.num_views
         shape, dt = {OUT_U8: ((n, 224, 224, 3), torch.uint8), OUT_F32: ((n, 3, 224, 224), torch.float32),
-                     OUT_F16: ((n, 3, 224, 224), torch.float16), OUT_RAW110: ((n, 110, 110), torch.float32)}[kind]
+                     OUT_F16: ((n, 3, 224, 224), torch.float16),
+                     OUT_RAW110: ((n, self.image_side, self.image_side), torch.float32)}[kind]
         result = torch.empty(shape, dtype=dt, device=origin.device)
         if n:
-            check(lib.vg_render_crops(ptr(origin), ptr(seg_off), seg_off.numel() - 1, ptr(self._d_rot),
-                                      self.num_views, ptr(self._d_lut), ptr(result), kind, stream_ptr(stream)),
-                  'vg_render_crops')
+            self._render(origin, seg_off, seg_off.numel() - 1, result, kind, stream_ptr(stream))
         return result
+
+    def _render(self, origin, seg_off, n_clusters, result, kind, sp):
+        if self._params is None:
+            check(lib.vg_render_crops(ptr(origin), ptr(seg_off), n_clusters, ptr(self._d_rot), self.num_views, ptr(self._d_lut),
+                                      ptr(result), kind, sp), 'vg_render_crops')
+        else:
+            check(lib.vg_render_crops_ex(ptr(origin), ptr(seg_off), n_clusters, ptr(self._d_rot), self.num_views, ptr(self._d_lut),
+                                         ctypes.byref(self._params), ptr(result), kind, sp), 'vg_render_crops_ex')
 
     # -- reference-shaped per-call interface (mv_utils.py:173-187) ---------------------------------
     def get_img(self, points):
         """points: [b,P,3] float32 CUDA tensor of origin-transformed cluster points ->
-        [b*V,3,110,110] float32 (three identical channels, as mv_utils.py:36)."""
+        [b*V,3,R-2,R-2] float32 for resolution R (three identical channels, as mv_utils.py:36)."""
         b, P, _ = points.shape
         seg = torch.arange(0, (b + 1) * P, P, dtype=torch.int32, device=points.device)
         raw = self.render_origin(points.reshape(b * P, 3).contiguous().float(), seg, out='raw110')
