@@ -7,6 +7,8 @@ Bars:
     what that leaves open is the FMA-or-not of torch's small matmul, tests/golden/make_golden.py::make_render_small), the others
     from the origin points through the reference's view matrices.
   * at (112, 8, 0.8, 0.2) the parameterised kernel equals k_render (vg_render_crops) byte for byte in all six output kinds.
+  * every crop slot is written by its own cluster through all three instantiations, at cluster counts on both sides of the 1024 up to
+    which workgroups take the clusters largest first.
   * the other output kinds are functions of the uint8 crop, as tests/test_render.py relates them at 112.
   * settings outside the ranges are VG_ERR_ARG and write nothing.
   * the renderer -> tower hand-over of PseudoLabelPipeline.classify at a non-default setting.
@@ -149,6 +151,58 @@ def test_hip_render_ex_at_the_shipped_setting_equals_render_crops(cuda, golden, 
     assert st == 0 and got.shape == want.shape
     assert torch.equal(got.view(torch.uint8), want.view(torch.uint8))
     assert bool(want.any())
+
+
+# ----------------------------------------------------------------------------------------------- 2b. which cluster a workgroup renders
+SLOT_POOL_SIZES = [3, 17, 40, 17, 9, 40]                  # two pairs of equal size: a tie broken wrongly leaves a slot unwritten
+SLOT_PATHS = {'fixed': None, 'ex12': (16, 8, 0.8, 0.2), 'ex16': (113, 8, 0.8, 0.2)}     # k_render, k_render_ex<12>, k_render_ex<16>
+
+
+def _render_slots(path, proj, clusters, dev):
+    """out_kind 3 of `clusters` through one of SLOT_PATHS into a NaN-filled buffer -> [C, side, side]"""
+    from vilgod_amd._lib import lib, ptr, stream_ptr, RenderParams
+    pts, seg = _pack(clusters, dev)
+    setting = SLOT_PATHS[path]
+    out = _out(3, len(clusters), (setting[0] if setting else 112) - 2, dev, fill=float('nan'))
+    if setting is None:
+        st = lib.vg_render_crops(ptr(pts), ptr(seg), len(clusters), ptr(proj._d_rot), 1, ptr(proj._d_lut), ptr(out), 3, stream_ptr())
+        torch.cuda.synchronize()
+    else:
+        st, out = _render_ex(proj, RenderParams(*setting), pts, seg, 3, out=out)
+    assert st == 0
+    return out
+
+
+@pytest.fixture(scope='module')
+def slot_pool(cuda):
+    """Six small point sets in view coordinates and, per path, each of them rendered alone (C = 1: the rank is trivially 0)."""
+    from vilgod_amd.projection import RealisticProjection
+    rng = np.random.default_rng(41)
+    pool = [(rng.normal(size=(P, 3)) * rng.uniform(0.3, 2.0, size=3)).astype(np.float32) for P in SLOT_POOL_SIZES]
+    assert not np.array_equal(pool[1], pool[3]) and not np.array_equal(pool[2], pool[5])
+    proj = RealisticProjection({}, device=cuda, views=IDENTITY)
+    alone = {path: torch.cat([_render_slots(path, proj, [m], cuda) for m in pool]) for path in SLOT_PATHS}
+    for a in alone.values():
+        assert bool(torch.isfinite(a).all()) and len({rr.sha(x.cpu().numpy()) for x in a}) == len(pool)      # six different images
+    return proj, pool, alone
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('C', [2, 7, 1024, 1025])
+@pytest.mark.parametrize('path', list(SLOT_PATHS))
+def test_hip_render_every_crop_slot_is_written_by_its_cluster(cuda, slot_pool, path, C):
+    """The block-to-cluster choice of csrc/render.hip (render_block_cluster: rank by point count, ties to the lower index, label order
+    above 1024 clusters) only decides WHEN a cluster is rendered: crop c is cluster c's image whatever the other clusters are.  Frames
+    that cycle through the pool in a shuffled order -- 1024 is the last ranked count, 1025 the first in label order -- equal, byte for
+    byte, the pool members rendered alone through the same entry point, and no slot keeps its NaN prefill."""
+    proj, pool, alone = slot_pool
+    order = np.random.default_rng(4).permutation(len(pool))
+    member = order[np.arange(C) % len(pool)]
+    assert SLOT_POOL_SIZES[member[0]] < SLOT_POOL_SIZES[member[1]]                   # label order is not rank order, already at C = 2
+    got = _render_slots(path, proj, [pool[m] for m in member], cuda)
+    assert not bool(torch.isnan(got).any())
+    want = alone[path][torch.from_numpy(member).to(cuda)]
+    assert got.shape == want.shape and torch.equal(got.view(torch.int32), want.view(torch.int32))
 
 
 # ----------------------------------------------------------------------------------------------- 3. the other output kinds

@@ -86,6 +86,13 @@ def test_cases_reach_the_edges_they_are_there_for(golden):
     assert (int(rows.min()) == 1 and int(rows.max()) == 110) or (int(cols.min()) == 1 and int(cols.max()) == 110)
 
 
+def test_render_kernels_use_no_scratch():
+    """k_render and both k_render_ex instantiations keep their running maxima in registers (csrc/render.hip, the per-slice opaque thread id)."""
+    from vilgod_amd import build
+    assert build.check_scratch('render.hip', 'k_render') == []
+    assert build.check_isa(sources=['render.hip']) == []
+
+
 # ----------------------------------------------------------------------------------------------- constructor
 def _cfg(**kw):
     c = dict(depth_bias=0.2, obj_ratio=0.8, bg_clr=0.0, resolution=112, depth=8, maxpool=dict(POOL), conv3d=dict(CONV),

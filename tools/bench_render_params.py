@@ -1,4 +1,4 @@
-"""Kernel time per frame of the two renderers of csrc/render.hip on the benchmark's frame shape (one synthetic 150k-point frame with
+"""Kernel time per frame of the two render kernels of csrc/render.hip on the benchmark's frame shape (one synthetic 150k-point frame with
 60 objects, its valid clusters x 4 views, single-channel fp16 patch rows = the product hand-over):
 
   default              k_render (vg_render_crops), the shipped setting compiled in

@@ -71,3 +71,23 @@ __device__ __forceinline__ float vg_wave_sum(float v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
     return v;
 }
+
+// Which of the 256 bins of `hist` holds rank k (0-based)?  Called by 256 threads (t = 0 .. 255: four whole waves) behind the barrier
+// that completes the histogram.  Exclusive prefix of the counts by wave scans (a serial walk by one thread cost ~16 k cycles per pass);
+// exactly one thread finds excl <= k < excl + count and writes sh[0] = the bin, sh[1] = the number of keys in the bins below it.
+// sh[2..5] hold the wave totals.  One barrier inside; the callers put another in front of reading sh[0..1].
+__device__ __forceinline__ void vg_rank_bin(const uint32_t* hist, uint32_t* sh, int t, int k) {
+    const uint32_t cnt = hist[t];
+    uint32_t inc = cnt;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t up = __shfl_up(inc, o);
+        if ((t & 63) >= o) inc += up;
+    }
+    if ((t & 63) == 63) sh[2 + (t >> 6)] = inc;
+    __syncthreads();
+    uint32_t base = 0;
+    for (int w = 0; w < (t >> 6); ++w) base += sh[2 + w];
+    const uint32_t excl = base + inc - cnt;
+    if (excl <= (uint32_t)k && (uint32_t)k < excl + cnt) { sh[0] = (uint32_t)t; sh[1] = excl; }
+}

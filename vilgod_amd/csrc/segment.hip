@@ -481,22 +481,7 @@ __device__ float vg_select_keys(const float* __restrict__ pts, int stride, int c
             vg_hist_add_wave(hist, (key >> shift) & 255u, in);
         }
         __syncthreads();
-        {   // the bin that holds rank k: exclusive prefix of the 256 counts by wave scans; exactly one thread finds it
-            const int t = threadIdx.x;
-            const uint32_t cnt = hist[t];
-            uint32_t inc = cnt;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const uint32_t up = __shfl_up(inc, o);
-                if ((t & 63) >= o) inc += up;
-            }
-            if ((t & 63) == 63) sh[2 + (t >> 6)] = inc;
-            __syncthreads();
-            uint32_t base = 0;
-            for (int w = 0; w < (t >> 6); ++w) base += sh[2 + w];
-            const uint32_t excl = base + inc - cnt;
-            if (excl <= (uint32_t)k && (uint32_t)k < excl + cnt) { sh[0] = (uint32_t)t; sh[1] = excl; }
-        }
+        vg_rank_bin(hist, sh, threadIdx.x, k);
         __syncthreads();
         prefix = (prefix << 8) | sh[0];
         k -= (int)sh[1];
