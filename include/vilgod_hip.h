@@ -386,6 +386,20 @@ int vg_cluster_ball_count(vg_cluster* h, const float* d_query, int nq, int qstri
 int vg_cluster_nearest(vg_cluster* h, const float* d_query, int nq, int qstride, float max_d2, int32_t* d_idx, float* d_d2,
                        void* stream);
 
+/* HOST ONLY, no GPU (like vg_hdbscan_tree_host): the geometry vg_cluster_mst[_nd] prunes with, evaluated on the CPU by the very
+ * functions its kernels call, so that the bounds can be checked without a device.  Pair i = (point i, query i), finite float32.
+ *   h_origin_in [3] f64 or NULL: the grid's origin; NULL: the origin the kernels derive from the float32 extremes h_bbox_lo/hi [3]
+ *   h_points [n,3] or NULL: NULL reads point i's cell from h_cell [n,3] instead of assigning it (cells outside the grid: VG_ERR_ARG)
+ *   h_queries [n,3] or NULL (then h_box_d2 / h_radius2 are not written)
+ * Outputs (each may be NULL): h_origin [3]; h_cell [n,3] cell of point i (512 x 512 x 64 cells of 0.4 m, points beyond the grid
+ * clamped into border cells); h_code [n] its Morton code; h_box_d2 [n,7] the walk's squared box distance from query i to the
+ * level-l node (2^l cells per axis) that holds point i, l = 0..6 -- a LOWER BOUND of the float64 (dx*dx + dy*dy) + dz*dz of the
+ * pair; h_radius2 [n,7] squared distance from query i to the nearest face of the 3 x 3 x 3 level-l nodes around its own (+inf
+ * where the grid ends first): no point outside those 27 nodes is nearer; h_lvl_off [8] offsets of the level tables 1..7 ([0] = 0). */
+int vg_cluster_geom_probe(const double* h_origin_in, const float* h_bbox_lo, const float* h_bbox_hi, const float* h_points,
+                          const float* h_queries, int n, double* h_origin, int32_t* h_cell, uint32_t* h_code, double* h_box_d2,
+                          double* h_radius2, int64_t* h_lvl_off);
+
 /* PP / ephemerality score from the per-neighbour-frame counts (pointcloud_utils.py:110-117 compute_ephe_score):
  * d_counts [n_frames][nq] int32 (row f = counts against neighbour frame f); seek_row >= 0: that row is the query frame
  * itself, 1 is subtracted (pointcloud_utils.py:90-91).  P = c / (sum c + 1e-8), H = sum(-P log(P + 1e-8)) / log(n_frames),

@@ -98,25 +98,41 @@ __device__ __forceinline__ int cl_xcd_block(int bid, int nwg) {
 }
 
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ unsigned int cl_spread6(unsigned int v) {   // 6 bits -> every third bit
+__host__ __device__ __forceinline__ unsigned int cl_spread6(unsigned int v) {   // 6 bits -> every third bit
     v &= 63u;
     v = (v | (v << 8)) & 0x300Fu;
     v = (v | (v << 4)) & 0x30C3u;
     v = (v | (v << 2)) & 0x9249u;
     return v;
 }
-__device__ __forceinline__ unsigned int cl_code(int cx, int cy, int cz) {
+__host__ __device__ __forceinline__ unsigned int cl_code(int cx, int cy, int cz) {
     unsigned int lo = cl_spread6(cx) | (cl_spread6(cy) << 1) | (cl_spread6(cz) << 2);
     unsigned int hi = ((unsigned int)cx >> 6) | (((unsigned int)cy >> 6) << 3);
     return (hi << 18) | lo;
 }
-__device__ __forceinline__ void cl_cell_of(const ClGrid& g, double x, double y, double z, int& cx, int& cy, int& cz) {
-    cx = (int)floor((x - g.ox) * (1.0 / CL_CELL));
-    cy = (int)floor((y - g.oy) * (1.0 / CL_CELL));
-    cz = (int)floor((z - g.oz) * (1.0 / CL_CELL));
-    cx = cx < 0 ? 0 : (cx > CL_NX - 1 ? CL_NX - 1 : cx);
-    cy = cy < 0 ? 0 : (cy > CL_NY - 1 ? CL_NY - 1 : cy);
-    cz = cz < 0 ? 0 : (cz > CL_NZ - 1 ? CL_NZ - 1 : cz);
+// THE faces of the grid: face i of an axis with origin o is the float64 value o + i * CL_CELL as computed (0.4 is not exact in binary,
+// so this is not the real number).  A level-l node c spans [face(c << l), face((c + 1) << l)): o + c * (CL_CELL * 2^l) rounds the
+// same real number, so every level computes the same faces.  Cells are assigned by these faces, not by the floor alone: the floor of
+// (v - o) * 2.5 puts a coordinate that sits on or next to a face into the neighbouring cell for some origins (ox = -10.4, x = 62.0:
+// floor gives cell 181, whose computed min face is 62.00000000000001), and a box that does not hold its own points is no lower bound.
+__host__ __device__ __forceinline__ int cl_cell_axis(double o, double v, int n) {
+    int c = (int)floor((v - o) * (1.0 / CL_CELL));
+    c = c < 0 ? 0 : (c > n - 1 ? n - 1 : c);
+    if (c > 0 && v < o + (double)c * CL_CELL) --c;                          // the floor is at most one cell off (errors ~1e-13 m)
+    else if (c < n - 1 && v >= o + (double)(c + 1) * CL_CELL) ++c;
+    return c;
+}
+__host__ __device__ __forceinline__ void cl_cell_of(const ClGrid& g, double x, double y, double z, int& cx, int& cy, int& cz) {
+    cx = cl_cell_axis(g.ox, x, CL_NX);
+    cy = cl_cell_axis(g.oy, y, CL_NY);
+    cz = cl_cell_axis(g.oz, z, CL_NZ);
+}
+// origin of one axis from the data's extremes: the data is centred in the grid when it fits, otherwise the grid is anchored at the
+// minimum (outliers clamp to border cells); floored to a multiple of the cell size
+__host__ __device__ __forceinline__ double cl_origin(double lo, double hi, double ext) {
+    const double span = hi - lo;
+    const double start = span < ext ? lo - 0.5 * (ext - span) : lo;
+    return floor(start / CL_CELL) * CL_CELL;
 }
 // cell_start is stored reversed (index NCODES - code) so that the "first point with code >= c" table is a
 // forward inclusive min-scan.
@@ -180,12 +196,7 @@ __global__ void k_cl_grid(ClGrid* g) {
     }
     const double ext[3] = {CL_NX * CL_CELL, CL_NY * CL_CELL, CL_NZ * CL_CELL};
     double o[3];
-    for (int a = 0; a < 3; ++a) {
-        // centre the data in the grid when it fits, otherwise anchor at the minimum (outliers clamp to border cells)
-        double span = hi[a] - lo[a];
-        double start = span < ext[a] ? lo[a] - 0.5 * (ext[a] - span) : lo[a];
-        o[a] = floor(start / CL_CELL) * CL_CELL;
-    }
+    for (int a = 0; a < 3; ++a) o[a] = cl_origin(lo[a], hi[a], ext[a]);
     g->ox = o[0]; g->oy = o[1]; g->oz = o[2];
 }
 
@@ -228,7 +239,7 @@ __device__ __forceinline__ double cl_d2(double ax, double ay, double az, double 
 }
 
 // squared distance from q to the nearest face of the level-l block [b-1, b+2) (faces clipped by the grid do not count)
-__device__ __forceinline__ double cl_block_radius2(const ClGrid& g, double qx, double qy, double qz, int bx, int by,
+__host__ __device__ __forceinline__ double cl_block_radius2(const ClGrid& g, double qx, double qy, double qz, int bx, int by,
                                                    int bz, int l) {
     const double s = CL_CELL * (double)(1 << l);
     double r = INFINITY;
@@ -257,7 +268,7 @@ __device__ __forceinline__ void cl_unpack(unsigned int e, int& l, int& x, int& y
 }
 // squared distance from q to the axis-aligned box of node (l,x,y,z); 0 inside.  Border nodes extend to infinity on
 // the outside (points beyond the grid are clamped INTO border cells).
-__device__ __forceinline__ double cl_box_d2(const ClGrid& g, double qx, double qy, double qz, int l, int x, int y, int z) {
+__host__ __device__ __forceinline__ double cl_box_d2(const ClGrid& g, double qx, double qy, double qz, int l, int x, int y, int z) {
     const double s = CL_CELL * (double)(1 << l);
     const int nb[3] = {CL_NX >> l, CL_NY >> l, CL_NZ >> l};
     const int c[3] = {x, y, z};
@@ -265,7 +276,7 @@ __device__ __forceinline__ double cl_box_d2(const ClGrid& g, double qx, double q
     double d2 = 0.0;
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
-        const double lo = o[a] + (double)c[a] * s, hi = lo + s;
+        const double lo = o[a] + (double)c[a] * s, hi = o[a] + (double)(c[a] + 1) * s;      // the faces cl_cell_axis assigns by (lo + s is not one)
         double d = 0.0;
         if (q[a] < lo && c[a] > 0) d = lo - q[a];
         else if (q[a] > hi && c[a] < nb[a] - 1) d = q[a] - hi;
@@ -834,6 +845,7 @@ __global__ __launch_bounds__(64) void k_cl_core_far(const float4* __restrict__ s
 
 // ---------------------------------------------------------------------------------------------
 // Boruvka
+#define CL_CYCLE 0x40000000            // bit of the edge counter: k_cl_b_compress found a cycle among the round's picks
 #define CL_NONE 0xFFFFFFFFFFFFFFFFull   // 'no candidate' (sorts after every weight, +inf included)
 
 __global__ void k_cl_b_init(int n, int* __restrict__ comp, int* __restrict__ counter, int* __restrict__ pt_b,
@@ -1171,7 +1183,7 @@ __global__ __launch_bounds__(NT) void k_cl_b_search(const float4* __restrict__ s
 #pragma unroll
                     for (int hb = 0; hb < 2; ++hb) {     // the same expressions as cl_box_d2, per axis
                         const int cc = c2[ax] + hb;
-                        const double lo = o3[ax] + (double)cc * s1, hi = lo + s1;
+                        const double lo = o3[ax] + (double)cc * s1, hi = o3[ax] + (double)(cc + 1) * s1;
                         double d = 0.0;
                         if (q3[ax] < lo && cc > 0) d = lo - q3[ax];
                         else if (q3[ax] > hi && cc < nbx[ax] - 1) d = q3[ax] - hi;
@@ -1451,6 +1463,7 @@ __global__ void k_cl_b_emit(int n, const int* __restrict__ comp, const int* __re
     }
     parent2[c] = p;
     int k = atomicAdd(counter, 1);
+    if (k >= n - 1) return;        // only after k_cl_b_compress met a cycle (CL_CYCLE): nothing is written beyond the n - 1 edges
     mst_a[k] = perm[sel_a[c]];
     mst_b[k] = perm[sel_b[c]];
     mst_w[k] = best_w[c];
@@ -1465,7 +1478,12 @@ __global__ void k_cl_b_compress(int n, int* __restrict__ comp, const int* __rest
     if (i >= n) return;
     const int old = comp[i];
     int r = old;
-    while (parent2[r] != r) r = parent2[r];
+    // Picks that are each component's minimum under the strict order form no cycle except mutual pairs (k_cl_b_emit breaks those), so
+    // this walk reaches a root.  A search that prunes wrongly breaks that; the walk then ends after n hops and marks the edge counter:
+    // the call returns VG_ERR_HIP (every later round is a no-op: flags[1]) instead of spinning on the device.
+    int hops = 0;
+    while (parent2[r] != r && hops < n) { r = parent2[r]; ++hops; }
+    if (parent2[r] != r) atomicOr(&flags[0], CL_CYCLE);
     // an absorbed root hands its point count to the new root (only new roots are written, and a new root never reads its own count here)
     if (old == i && r != i) atomicAdd(&csize[r], csize[i]);
     comp[i] = r;
@@ -1853,6 +1871,53 @@ int vg_cluster_nearest(vg_cluster* h, const float* d_query, int nq, int qstride,
     return VG_OK;
 }
 
+/* HOST ONLY (no GPU): the geometry the walks prune with, evaluated by the functions the kernels call (cl_origin, cl_cell_of,
+ * cl_code, cl_box_d2, cl_block_radius2, cl_lvl_off are __host__ __device__).  Pair i = (point i, query i).
+ *   h_origin_in [3] f64 or NULL: the origin; NULL: cl_origin of the float32 extremes h_bbox_lo / h_bbox_hi [3]
+ *   h_points [n,3] f32 or NULL: NULL reads the cells from h_cell instead of assigning them
+ *   h_queries [n,3] f32 or NULL (then h_box_d2 / h_radius2 are not written)
+ *   h_origin [3]; h_cell [n,3]; h_code [n]; h_box_d2 [n,7]: cl_box_d2(query i, level-l node of point i's cell), l = 0..6;
+ *   h_radius2 [n,7]: cl_block_radius2 of query i around the level-l node of ITS OWN cell; h_lvl_off [8]: cl_lvl_off(l), l = 1..7 ([0] = 0)
+ *   (every output may be NULL) */
+int vg_cluster_geom_probe(const double* h_origin_in, const float* h_bbox_lo, const float* h_bbox_hi, const float* h_points,
+                          const float* h_queries, int n, double* h_origin, int32_t* h_cell, uint32_t* h_code, double* h_box_d2,
+                          double* h_radius2, int64_t* h_lvl_off) {
+    if (n < 0 || (!h_origin_in && (!h_bbox_lo || !h_bbox_hi)) || (n > 0 && !h_points && !h_cell)) return VG_ERR_ARG;
+    ClGrid g;
+    memset(&g, 0, sizeof(g));
+    g.inf = INFINITY;
+    const double ext[3] = {CL_NX * CL_CELL, CL_NY * CL_CELL, CL_NZ * CL_CELL};
+    double o[3];
+    for (int a = 0; a < 3; ++a) o[a] = h_origin_in ? h_origin_in[a] : cl_origin((double)h_bbox_lo[a], (double)h_bbox_hi[a], ext[a]);
+    g.ox = o[0]; g.oy = o[1]; g.oz = o[2];
+    if (h_origin) for (int a = 0; a < 3; ++a) h_origin[a] = o[a];
+    if (h_lvl_off) {
+        h_lvl_off[0] = 0;
+        for (int l = 1; l <= CL_LMAX + 1; ++l) h_lvl_off[l] = (int64_t)cl_lvl_off(l);
+    }
+    const int nb[3] = {CL_NX, CL_NY, CL_NZ};
+    for (int i = 0; i < n; ++i) {
+        int c[3];
+        if (h_points) cl_cell_of(g, (double)h_points[3 * (size_t)i], (double)h_points[3 * (size_t)i + 1], (double)h_points[3 * (size_t)i + 2], c[0], c[1], c[2]);
+        else
+            for (int a = 0; a < 3; ++a) {
+                c[a] = h_cell[3 * (size_t)i + a];
+                if (c[a] < 0 || c[a] >= nb[a]) return VG_ERR_ARG;
+            }
+        if (h_cell && h_points) for (int a = 0; a < 3; ++a) h_cell[3 * (size_t)i + a] = c[a];
+        if (h_code) h_code[i] = cl_code(c[0], c[1], c[2]);
+        if (!h_queries) continue;
+        const double qx = (double)h_queries[3 * (size_t)i], qy = (double)h_queries[3 * (size_t)i + 1], qz = (double)h_queries[3 * (size_t)i + 2];
+        int q[3];
+        cl_cell_of(g, qx, qy, qz, q[0], q[1], q[2]);
+        for (int l = 0; l <= CL_LMAX; ++l) {
+            if (h_box_d2) h_box_d2[7 * (size_t)i + l] = cl_box_d2(g, qx, qy, qz, l, c[0] >> l, c[1] >> l, c[2] >> l);
+            if (h_radius2) h_radius2[7 * (size_t)i + l] = cl_block_radius2(g, qx, qy, qz, q[0] >> l, q[1] >> l, q[2] >> l, l);
+        }
+    }
+    return VG_OK;
+}
+
 /* Exact core distances + exact MST of the mutual reachability graph.  SYNCHRONOUS on `stream` (one small
  * device->host counter read per Boruvka round).
  *   d_points [n,stride] f32; dim = 3, 4 or 5 leading columns form the clustering space (x,y,z first: the cell grid and
@@ -1987,6 +2052,10 @@ int vg_cluster_mst_nd(vg_cluster* h, const float* d_points, int n, int stride, i
             edges = e;
             if (edges >= n - 1 && !needed) needed = r;
         }
+    }
+    if (edges & CL_CYCLE) {
+        fprintf(stderr, "[vilgod_hip] vg_cluster_mst: the picks of a Boruvka round formed a cycle (a pruning bound is wrong)\n");
+        return VG_ERR_HIP;
     }
     rounds = needed;
     if (h_rounds) *h_rounds = rounds;
