@@ -349,6 +349,84 @@ def test_pack_clusters_host_equals_numpy_form():
             assert g.dtype == w.dtype and np.array_equal(g, w)
 
 
+def concatenated_sublists(index, seg, rows):
+    """The sub-lists of the clusters `rows`, written out: what every caller of frame_state.cluster_sublists used to build in place."""
+    parts = [index[seg[c]:seg[c + 1]] for c in rows]
+    return (np.concatenate(parts).astype(np.int32) if parts else np.zeros(0, np.int32),
+            np.r_[0, np.cumsum([len(p) for p in parts])].astype(np.int32))
+
+
+def sublist_case_700():
+    """700 clusters of 0 .. 12 points (a few thousand in all, empty ones among them) and a seeded random subset of them, ascending."""
+    rng = np.random.default_rng(700)
+    seg = np.r_[0, np.cumsum(rng.integers(0, 13, 700))].astype(np.int32)
+    index = rng.permutation(int(seg[-1]) + 50)[:int(seg[-1])].astype(np.int32)
+    return index, seg, np.flatnonzero(rng.random(700) < 0.4)
+
+
+def test_cluster_sublists_equal_the_written_out_concatenation():
+    """frame_state.cluster_sublists / sublist_offsets / FrameState.sublists against the concatenation and running sum the pipeline and the
+    stage dispatcher each wrote out: no clusters, no rows, one row, all rows, rows out of order, an empty cluster in the middle, 700
+    clusters with a random subset -- values and dtypes (int32, int32)."""
+    from vilgod_amd.frame_state import FrameState, cluster_sublists, sublist_offsets
+    index3, seg3 = np.array([5, 1, 4, 9, 9, 2, 7], np.int32), np.array([0, 2, 3, 7], np.int32)
+    gap = np.array([0, 3, 3, 7], np.int32)                       # the middle cluster holds no points
+    index700, seg700, rows700 = sublist_case_700()
+    assert (np.diff(seg700) == 0).any() and 100 < len(rows700) < 600 and 2000 < len(index700) < 8000
+    cases = [(np.zeros(0, np.int32), np.zeros(1, np.int32), []), (index3, seg3, []), (index3, seg3, [1]), (index3, seg3, [0, 1, 2]),
+             (index3, seg3, [2, 0]), (index3, gap, [0, 1, 2]), (index3, gap, [1]), (index3, gap, np.array([2, 1])),
+             (index700, seg700, rows700), (index700, seg700, np.arange(700)), (index700, seg700, rows700[::-1])]
+    for index, seg, rows in cases:
+        want = concatenated_sublists(index, seg, rows)
+        fs = FrameState(0, np.eye(4), np.eye(4))
+        fs.set_clusters(np.arange(len(seg) - 1), index, seg)
+        for got in (cluster_sublists(index, seg, rows), fs.sublists(rows), (want[0], sublist_offsets(seg, rows))):
+            for g, w in zip(got, want):
+                assert g.dtype == np.int32 and g.shape == w.shape and np.array_equal(g, w), (seg, rows)
+    empty = cluster_sublists(index3, seg3, [])
+    assert empty[0].shape == (0,) and empty[1].tolist() == [0]
+
+
+@pytest.mark.parametrize('off', [(), (1, 3)])
+def test_vote_step_writes_what_both_callers_wrote(off):
+    """PseudoLabelPipeline.vote_classes against the lines `label` and the classification stage each held: fine classes -> mapped
+    names -> frame_state.vote -> FrameState.set_classes.  The expected entry is written out here with `vote` and `set_classes`."""
+    from vilgod_amd.frame_state import FrameState, vote
+    from vilgod_amd.pipeline import PseudoLabelPipeline, default_preprocessor_cfg
+    import types
+    C, V = 5, 4
+    pipe = PseudoLabelPipeline.__new__(PseudoLabelPipeline)          # the class tables alone: no device behind this handle
+    pipe._init_classes(default_preprocessor_cfg()['clip'])
+    pipe.projection = types.SimpleNamespace(num_views=V)
+    which = np.ones(C, bool)
+    which[list(off)] = False
+    n = int(which.sum())
+    rng = np.random.default_rng(54)
+    top1 = rng.integers(0, len(pipe.class_list), n * V)             # flat, as the score kernel leaves them
+    top1[:V] = [0, 0, 9, 9]                                         # a tie between two mapped names: the mean score decides
+    score = rng.random(n * V)                                       # float64 on purpose: the step stores float32
+    frames = [FrameState(0, np.eye(4), np.eye(4)) for _ in range(2)]
+    for fs in frames:
+        fs.set_clusters(np.arange(C), np.arange(2 * C, dtype=np.int32), np.arange(0, 2 * C + 1, 2, dtype=np.int32))
+    got, want = frames
+    names, win, final = pipe.vote_classes(got, 'clip', which, top1, score)
+    w_names, w_fine_names = np.array(pipe.mapped_names, dtype=object), np.array(pipe.class_list, dtype=object)
+    fine, sc = top1.reshape(n, V), score.reshape(n, V).astype(np.float32)
+    mapped = pipe.fine_to_mapped[fine]
+    w_win, w_final = vote(mapped, sc, pipe.mapped_names)
+    want.set_classes('clip', which, w_names[mapped], w_fine_names[fine], sc, w_names[w_win], w_final)
+    assert names.dtype == object and names.tolist() == pipe.mapped_names == ['Background', 'Cyclist', 'Pedestrian', 'Vehicle']
+    assert win.dtype == w_win.dtype and np.array_equal(win, w_win) and len(win) == n
+    assert final.dtype == np.float32 and np.array_equal(final, w_final)
+    assert set(got.cls) == {'clip'} and set(got.cls['clip']) == set(want.cls['clip'])
+    for k, w in want.cls['clip'].items():
+        g = got.cls['clip'][k]
+        assert g.dtype == w.dtype and g.shape == w.shape and np.array_equal(g, w), k
+    e = got.cls['clip']
+    assert e['has'].tolist() == which.tolist() and e['score'].shape == (C, V) and not e['score'][list(off)].any()
+    assert e['pred'][0].tolist() == ['Vehicle', 'Vehicle', 'Pedestrian', 'Pedestrian'] and e['detailed'][0, 2] == 'pedestrian'
+
+
 @pytest.mark.parametrize('family', ['pp64', 'w4'])
 def test_profile_summary_splits_the_projection_gemm_per_kind(tmp_path, family):
     """tools/summarize_profiles.py (VERDICT r4 task 2: FETCH / WRITE / SQ counters per GEMM KIND): a fabricated rocprofv3 run -- two frames of two

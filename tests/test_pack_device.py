@@ -325,6 +325,23 @@ def test_selection_equals_numpy_concatenation(cuda):
             masks['largest'] = largest
         for name, keep in masks.items():
             _check_select(index, seg, keep.astype(np.uint8), cuda, (family, n, name))
+    # frame_state.select_rows_device (the pipeline's and the stage dispatcher's cut of some clusters, trimmed to what the kernel wrote)
+    # against the host's cluster_sublists, itself pinned to the written-out concatenation in test_host.py
+    from test_host import sublist_case_700
+    from vilgod_amd.frame_state import cluster_sublists, select_rows_device
+    index700, seg700, rows700 = sublist_case_700()
+    three = (np.array([5, 1, 4, 9, 9, 2, 7], np.int32), np.array([0, 2, 3, 7], np.int32))
+    for index, seg, rows, on_device in [(np.array([3, 0, 2], np.int32), np.array([0, 3], np.int32), [0], False), (*three, [1], False),
+                                        (*three, [0, 1, 2], False), (index700, seg700, np.arange(700), False),
+                                        (index700, seg700, rows700, False), (index700, seg700, rows700, True)]:
+        C = len(seg) - 1
+        w_index, w_seg = cluster_sublists(index, seg, rows)
+        keep = rows
+        if on_device:                                       # the verdict as a filter kernel leaves it: uint8 [C], already on the device
+            keep = torch.from_numpy(np.isin(np.arange(C), rows).astype(np.uint8)).to(cuda)
+        g_index, g_seg = select_rows_device(torch.from_numpy(index).to(cuda), torch.from_numpy(seg).to(cuda), C, w_seg, keep)
+        assert g_index.dtype == torch.int32 and g_seg.dtype == torch.int32 and g_index.is_cuda and g_seg.is_cuda
+        assert np.array_equal(g_index.cpu().numpy(), w_index) and np.array_equal(g_seg.cpu().numpy(), w_seg), (C, len(rows), on_device)
 
 
 # ---- GPU: refusals ----------------------------------------------------------------------------------------------------------------------

@@ -128,6 +128,30 @@ def select_clusters_device(d_index, d_seg, n_clusters, d_valid, n_index=None, wo
     return o_index, o_seg, counts
 
 
+def sublist_offsets(seg_off, rows):
+    """Offsets int32 [len(rows) + 1] of the packed lists of the clusters `rows` alone (any order; no rows: [0])."""
+    rows = np.asarray(rows, dtype=np.int64)
+    return np.r_[0, np.cumsum(seg_off[rows + 1] - seg_off[rows])].astype(np.int32)
+
+
+def cluster_sublists(index, seg_off, rows):
+    """The packed lists of the clusters `rows` alone, in the order of `rows` (empty clusters allowed) -> (index int32, seg int32)."""
+    parts = [index[seg_off[c]:seg_off[c + 1]] for c in rows]
+    sub = np.concatenate(parts) if parts else np.zeros(0, np.int32)
+    return np.ascontiguousarray(sub, dtype=np.int32), sublist_offsets(seg_off, rows)
+
+
+def select_rows_device(d_index, d_seg, n_clusters, seg, keep):
+    """`cluster_sublists` cut on the device from the lists held there (select_clusters_device).  keep: the clusters as STRICTLY INCREASING
+    host rows, or as the CUDA uint8 [n_clusters] verdict a filter kernel left on the device (no upload then).  seg: their
+    `sublist_offsets` on the host: it sizes what the kernel writes, so nothing is read back.  -> (d_index, d_seg [len(seg)]) CUDA int32."""
+    import torch
+    if not isinstance(keep, torch.Tensor):
+        keep = torch.from_numpy(np.isin(np.arange(n_clusters), keep).astype(np.uint8)).to(d_index.device)
+    o_index, o_seg, _ = select_clusters_device(d_index, d_seg, n_clusters, keep)
+    return o_index[:int(seg[-1])], o_seg[:len(seg)]
+
+
 def vote(class_ids, scores, class_names_sorted):
     """LidarFrame.update_object_classes (lidar_frame.py:269-285) for all detections at once.
     class_ids: [C,V] indices into `class_names_sorted` (ALPHABETICAL order = np.unique order); scores [C,V] float32.
@@ -225,6 +249,9 @@ class FrameState:
 
     def cluster_index(self, c):
         return self.index[self.seg_off[c]:self.seg_off[c + 1]]
+
+    def sublists(self, rows):
+        return cluster_sublists(self.index, self.seg_off, rows)
 
     def set_classes(self, key, which, pred, detailed, score, name, final_score):
         """which: bool [C] detections that were classified; the arrays have one row per True entry."""

@@ -26,8 +26,8 @@ from scipy.spatial.transform import Rotation
 
 from ._lib import (lib, ptr, stream_ptr, check, FilterParams, FILTER_NAMES, FILTER_AND_REQUIRED, FILTER_AND, FILTER_OR, FILTER_NSTATS,
                    FILTER_FLAG_HULL_OVERFLOW, BOX_FLAG_HULL_OVERFLOW)
-from .frame_state import (FrameState, pack_clusters, vote, static_from_entropy, pack_clusters_device, select_clusters_device,
-                          PACK_MAX_LABEL_BOUND)
+from .frame_state import (FrameState, pack_clusters, vote, static_from_entropy, pack_clusters_device, select_rows_device,
+                          sublist_offsets, PACK_MAX_LABEL_BOUND)
 from . import patchworkpp as gpw
 from .hdbscan import HDBSCAN
 from .projection import RealisticProjection, VIEWS_4, VIEWS_6
@@ -143,12 +143,8 @@ class PseudoLabelPipeline:
         clip_cfg = _get(cfg, 'clip')
         self.clip = clip if clip is not None else ClipWrapper(clip_cfg, clip_model_path, device=self.device, dtype=vit_dtype)
         self.vit_dtype = vit_dtype
-        self.class_list = list(_get(clip_cfg, 'class_list'))
-        mapping = _get(clip_cfg, 'class_mapping')
-        self.mapped_names = sorted(set(mapping[c] for c in self.class_list))          # alphabetical = np.unique order
-        self.fine_to_mapped = np.array([self.mapped_names.index(mapping[c]) for c in self.class_list])
+        self._init_classes(clip_cfg)
         self.class_names = list(_get(cfg, 'class_names', ['Vehicle', 'Pedestrian', 'Cyclist']))
-        self.cls_key = f"{_get(clip_cfg, 'name', 'clip')}_" + '_'.join(str(_get(clip_cfg, 'prompt_template')).format('').split(' ')[:-1])
         self.plane_seed = int(plane_seed)
         if box_mode not in ('reference', 'fast'):
             raise ValueError("box_mode: 'reference' (the reference's boxes: qhull vertex order, closing edge dropped) or 'fast' "
@@ -183,6 +179,15 @@ class PseudoLabelPipeline:
         self.vit_stream = None
         self._clip_cfg, self._clip_model_path, self._mcfg, self._n_views = clip_cfg, clip_model_path, mcfg, n_views
         self._workers = None
+
+    def _init_classes(self, clip_cfg):
+        """The class tables of `vote_classes` from the clip node: fine classes, their mapped names, the key the results go under."""
+        self.class_list = list(_get(clip_cfg, 'class_list'))
+        mapping = _get(clip_cfg, 'class_mapping')
+        self.mapped_names = sorted(set(mapping[c] for c in self.class_list))          # alphabetical = np.unique order
+        self.fine_to_mapped = np.array([self.mapped_names.index(mapping[c]) for c in self.class_list])
+        self._name_arrays = np.array(self.mapped_names, dtype=object), np.array(self.class_list, dtype=object)
+        self.cls_key = f"{_get(clip_cfg, 'name', 'clip')}_" + '_'.join(str(_get(clip_cfg, 'prompt_template')).format('').split(' ')[:-1])
 
     # ---- several frames in flight ------------------------------------------------------------------------------
     def _clone_for_worker(self):
@@ -709,6 +714,10 @@ class PseudoLabelPipeline:
               'vg_cluster_medians')
         return out
 
+    def lists_to_device(self, index, seg):
+        """Packed cluster lists of the host -> (d_index, d_seg) CUDA int32, queued on the current stream."""
+        return tuple(torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(self.device) for a in (index, seg))
+
     def xy_to_host_async(self, d_X):
         """Start the D2H copy of points_ref_wo_ground[:, :2] into this worker's pinned buffer (reference box mode reads each
         cluster's xy points once on the host, vilgod_amd/boxes.py).  -> (host array view, event to wait for)."""
@@ -743,8 +752,7 @@ class PseudoLabelPipeline:
         if C == 0:
             return np.zeros((0, 7))
         if d_index is None:
-            d_index = torch.from_numpy(np.ascontiguousarray(index, dtype=np.int32)).to(self.device)
-            d_seg = torch.from_numpy(np.ascontiguousarray(seg, dtype=np.int32)).to(self.device)
+            d_index, d_seg = self.lists_to_device(index, seg)
         if name != 'minimum_bounding_rectangle':
             return self.lshape_boxes(d_X, d_index, d_seg, name, args)[0].cpu().numpy()
         if self.box_mode == 'fast':
@@ -768,8 +776,7 @@ class PseudoLabelPipeline:
         """Reference mode: start the host part (vilgod_amd/boxes.py) in a helper process; .result() -> [C,7] boxes."""
         from .boxes import submit_reference_boxes
         if d_index is None:
-            d_index = torch.from_numpy(np.ascontiguousarray(index, dtype=np.int32)).to(self.device)
-            d_seg = torch.from_numpy(np.ascontiguousarray(seg, dtype=np.int32)).to(self.device)
+            d_index, d_seg = self.lists_to_device(index, seg)
         if zmin is None:
             zmin, zmax = self.z_extent(d_X, d_index, d_seg)
         if xy_host is None:
@@ -871,25 +878,17 @@ class PseudoLabelPipeline:
             return out
         # several frames in flight: ground / entropy / the per-frame clustering rows are sequence-level work on the caller's
         # stream; clustering + label transfer + filters + classification + boxes of a frame run on a worker stream
-        workers = self._ensure_workers(n_workers)
         parts = TwoFrameClusterer(self.cluster_model, n_frames=n_frames, seed=seed).precompute_parts(X_list, ent_list, mapper=mapper) if use_two else None
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream(self.device))
 
         def run(worker, i):
             fs, d_ref, d_X, gidx = prepared[i]
-            with torch.cuda.stream(worker.stream):
-                worker.stream.wait_event(ev)
-                if use_two:
-                    labels, probs = TwoFrameClusterer(worker.cluster_model, n_frames=n_frames, seed=seed, parts=parts).labels(i, X_list, ent_list)
-                else:
-                    labels, probs = worker.cluster(d_X)
-                r = worker.label(fs, d_ref, d_X, gidx, labels, probs, entropy=ent_host[i])
-                worker.stream.synchronize()
-            return r
+            if use_two:
+                labels, probs = TwoFrameClusterer(worker.cluster_model, n_frames=n_frames, seed=seed, parts=parts).labels(i, X_list, ent_list)
+            else:
+                labels, probs = worker.cluster(d_X)
+            return worker.label(fs, d_ref, d_X, gidx, labels, probs, entropy=ent_host[i])
 
-        futures = [workers[i % n_workers].thread.submit(run, workers[i % n_workers], i) for i in range(len(prepared))]
-        return [f.result() for f in futures]
+        return self.map_workers(range(len(prepared)), run, n_workers)
 
     def pack_device(self, labels, probs):
         """Cluster packing on the device (csrc/pack.hip) for labels / probabilities that are CUDA tensors (the device hierarchy's) or host
@@ -942,75 +941,98 @@ class PseudoLabelPipeline:
             return h_ids.numpy().copy(), h_index.numpy().copy(), h_seg.numpy().copy()
         return index[:P], seg[:C + 1], fetch
 
+    def pack_frame(self, labels, probs):
+        """A frame's cluster lists by `self.pack` -> ((d_index, d_seg) of `pack_device`, or None when the host packed the frame: pack='host'
+        or a frame `pack_device` refuses; fetch() -> (ids, index, seg) on the host: pack='device' waits for their copy there)."""
+        packed = self.pack_device(labels, probs) if self.pack == 'device' else None
+        if packed is not None:
+            return packed[:2], packed[2]
+        if isinstance(labels, torch.Tensor):             # (device packing refused the frame: a label beyond its bound)
+            labels, probs = labels.cpu().numpy(), None if probs is None else probs.cpu().numpy()
+        lists = pack_clusters(labels, probs, self.prob_threshold)                    # lidar_frame.py:154-248
+        return None, lambda: lists
+
+    def static_flags(self, entropy, index, seg):
+        """`Detection.static` of the packed clusters from the per-point entropy scores (host float32 [M]), with the thresholds of
+        clustering.entropy_score_filter; what the node does not set keeps `static_from_entropy`'s defaults (30 / 0.5)."""
+        ecfg = _get(_get(self.cfg, 'clustering'), 'entropy_score_filter', None)
+        args = {k: float(_get(ecfg, k)) for k in ('percentile', 'min_percentile_pp_score') if ecfg and _get(ecfg, k) is not None}
+        return static_from_entropy(entropy, index, seg, **args)
+
+    def plane_and_filter(self, fs, d_ref, d_X, d_index, d_seg, gidx=None, entropy=None, queued=None):
+        """[C2] + [C1]: ground plane (lidar_frame.py:96-109; [0,0,1,0] when no active filter reads it) and filters of the packed clusters.
+        Writes fs.ground_plane_model_ref / valid / filter_dict / filtered -> (valid, stats) as `filter` returns them.  gidx: the ground
+        indices on the device (default: fs's, uploaded).  queued(): called once the launches are queued, before the verdict is read
+        back: host work that may wait meanwhile, and the place of a late FrameState.set_clusters (it resets `valid`)."""
+        if self._filters['use_plane']:
+            if gidx is None:
+                gidx = torch.from_numpy(np.asarray(fs.ground_point_indices)).to(self.device)
+            fs.ground_plane_model_ref = self.ground_plane(d_ref, gidx)
+        else:
+            fs.ground_plane_model_ref = np.array([0.0, 0.0, 1.0, 0.0])
+        valid, stats = self.filter(d_X, d_index, d_seg, fs.ground_plane_model_ref, entropy=entropy)
+        if queued is not None:
+            queued()
+        fs.valid = valid.cpu().numpy().astype(bool)
+        if self.last_filter_dict is not None:
+            fs.filter_dict = self.last_filter_dict
+        fs.filtered = True
+        return valid, stats
+
+    def vote_classes(self, fs, key, which, top1, score):
+        """[D10]: the views' top-1 fine classes and scores (host, one row of `num_views` per True entry of `which`) -> mapped names,
+        vote, fs.set_classes(key, ...).  -> (names: the mapped names as an object array, win [rows] indices into it, final [rows])."""
+        V = self.projection.num_views
+        fine = top1.reshape(-1, V)
+        sc = score.reshape(-1, V).astype(np.float32)
+        mapped = self.fine_to_mapped[fine]
+        win, final = vote(mapped, sc, self.mapped_names)
+        names, fine_names = self._name_arrays
+        fs.set_classes(key, which, names[mapped], fine_names[fine], sc, names[win], final)
+        return names, win, final
+
     def label(self, fs, d_ref, d_X, gidx, labels, probs, entropy=None, t=None, t0=None, tick=None, before_classify=None):
         """Everything after clustering: detections, static flags, filters, classification, boxes, results."""
-        t = {} if t is None else t
+        t = self.timings = {} if t is None else t
         if tick is None:
             tick = lambda name, t0: time.perf_counter()
             t0 = time.perf_counter()
         # per-crop score matrix of THIS frame (empty unless the frame reaches classification): never a previous frame's
         self.last_probs = torch.zeros((0, len(self.class_list)), dtype=torch.float32, device=self.device)
-        packed = self.pack_device(labels, probs) if self.pack == 'device' else None
-        if packed is None:
-            if isinstance(labels, torch.Tensor):         # (device packing refused the frame: a label beyond its bound)
-                labels, probs = labels.cpu().numpy(), None if probs is None else probs.cpu().numpy()
-            ids, index, seg = pack_clusters(labels, probs, self.prob_threshold)
-            d_index = d_seg = None
-        else:
-            d_index, d_seg, fetch = packed
-            if entropy is not None or d_seg.numel() == 1:
-                ids, index, seg = fetch()                # static_from_entropy reads the lists on the host right away
-            else:
-                ids = index = seg = None                 # fetched behind the plane / filter launches
-        C = (d_seg.numel() - 1) if ids is None else len(ids)
-        if ids is not None:
-            fs.set_clusters(ids, index, seg)
+        d_lists, fetch = self.pack_frame(labels, probs)
+        # pack='device': static_flags reads the lists on the host right away; otherwise they are fetched behind the plane / filter launches
+        late = d_lists is not None and entropy is None and d_lists[1].numel() > 1
+        if not late:
+            fs.set_clusters(*fetch())
+        C = (d_lists[1].numel() - 1) if late else fs.n_detections
         if entropy is not None and C:
-            ecfg = _get(_get(self.cfg, 'clustering'), 'entropy_score_filter', None)
-            fs.static = static_from_entropy(entropy, index, seg, percentile=float(_get(ecfg, 'percentile', 30) if ecfg else 30),
-                                            min_percentile_pp_score=float(_get(ecfg, 'min_percentile_pp_score', 0.5) if ecfg else 0.5))
+            fs.static = self.static_flags(entropy, fs.index, fs.seg_off)
         result = {'boxes_lidar': np.zeros((0, 7)), 'name': np.array([]), 'score': np.array([]), 'moving': np.array([])}
         if C == 0:
-            self.timings = t
             return fs, result
-        if d_index is None:
-            d_index = torch.from_numpy(index).to(self.device)
-            d_seg = torch.from_numpy(seg).to(self.device)
+        d_index, d_seg = d_lists if d_lists is not None else self.lists_to_device(fs.index, fs.seg_off)
         self._mark('pack_clusters+h2d')
         xy_host = xy_ev = None
         if self.box_mode == 'reference':
             xy_host, xy_ev = self.xy_to_host_async(d_X)            # lands while the plane fit / filters / classification run
-        plane = self.ground_plane(d_ref, gidx) if self._filters['use_plane'] else np.array([0.0, 0.0, 1.0, 0.0])
-        fs.ground_plane_model_ref = plane
-        valid, stats = self.filter(d_X, d_index, d_seg, plane, entropy=entropy)
-        if ids is None:
-            ids, index, seg = fetch()                    # pack='device': the lists' copy was queued in front of the plane fit
-            fs.set_clusters(ids, index, seg)
-        fs.valid = valid.cpu().numpy().astype(bool)
-        if self.last_filter_dict is not None:
-            fs.filter_dict = self.last_filter_dict
+        # (pack='device': the lists' copy was queued in front of the plane fit)
+        valid, stats = self.plane_and_filter(fs, d_ref, d_X, d_index, d_seg, gidx=gidx, entropy=entropy,
+                                             queued=(lambda: fs.set_clusters(*fetch())) if late else None)
         st = stats.cpu().numpy() if self.box_mode == 'reference' else None     # (the same kernel wrote it: no further wait)
-        fs.filtered = True
         self._mark('plane+filter')
         t0 = tick('filter', t0)
         vrows = np.flatnonzero(fs.valid)
         if len(vrows) == 0:
-            self.timings = t
             return fs, result
         # packed sub-list of the valid clusters (classification and boxes are `valid_only`, preprocessing.yaml:81,89)
-        if packed is not None:
+        if d_lists is not None:
             # pack='device': the sub-lists are cut on the device from the filter's own verdict bytes (csrc/pack.hip vg_pack_select); their
             # sizes follow from the host's copy of the verdict, the host's copy of the lists is built only if host code reads it
-            v_seg = np.r_[0, np.cumsum(seg[vrows + 1] - seg[vrows])].astype(np.int32)
-            d_vindex, d_vseg, _ = select_clusters_device(d_index, d_seg, C, valid, n_index=len(index))
-            d_vindex, d_vseg = d_vindex[:int(v_seg[-1])], d_vseg[:len(vrows) + 1]
-            v_index = None
+            v_index, v_seg = None, sublist_offsets(fs.seg_off, vrows)
+            d_vindex, d_vseg = select_rows_device(d_index, d_seg, C, v_seg, valid)
         else:
-            parts = [index[seg[c]:seg[c + 1]] for c in vrows]
-            v_index = np.concatenate(parts)
-            v_seg = np.r_[0, np.cumsum([len(p) for p in parts])].astype(np.int32)
-            d_vindex = torch.from_numpy(v_index).to(self.device)
-            d_vseg = torch.from_numpy(v_seg).to(self.device)
+            v_index, v_seg = fs.sublists(vrows)
+            d_vindex, d_vseg = self.lists_to_device(v_index, v_seg)
         if before_classify is not None:
             before_classify()                    # the frame's clustering / filtering is done, its crops are about to be queued
         self._mark('valid_lists')
@@ -1023,7 +1045,7 @@ class PseudoLabelPipeline:
             # request used to sit in front of the render, on the frame's critical path)
             xy_ev.synchronize()
             if v_index is None:
-                v_index = np.concatenate([index[seg[c]:seg[c + 1]] for c in vrows])        # (the helper processes' request reads it)
+                v_index = fs.sublists(vrows)[0]          # (the helper processes' request reads it)
             box_fut = self.fit_boxes_async(d_X, v_index, v_seg, d_vindex, d_vseg, xy_host=xy_host, zmin=st[vrows, 1], zmax=st[vrows, 2])
         self._mark('encode+scores')              # (incl. the box request sent while the GPU encodes)
         if box_fut is None:
@@ -1034,15 +1056,7 @@ class PseudoLabelPipeline:
             box = box_fut.result()
         self._mark('scores_d2h+box_wait')
         t0 = tick('classify+boxes', t0)
-        V = self.projection.num_views
-        nv = len(vrows)
-        fine = top1.reshape(nv, V)
-        sc = score.reshape(nv, V).astype(np.float32)
-        mapped = self.fine_to_mapped[fine]
-        win, final = vote(mapped, sc, self.mapped_names)
-        names = np.array(self.mapped_names, dtype=object)
-        fine_names = np.array(self.class_list, dtype=object)
-        fs.set_classes(self.cls_key, fs.valid.copy(), names[mapped], fine_names[fine], sc, names[win], final)
+        names, win, final = self.vote_classes(fs, self.cls_key, fs.valid.copy(), top1, score)
         fs.boxes = np.full((C, 7), np.nan)
         fs.boxes[vrows] = box
         # [F1] evaluate_sequence (zero_shot_detector.py:832-857)
@@ -1053,6 +1067,5 @@ class PseudoLabelPipeline:
                   'moving': np.zeros(int(keep.sum()), dtype=bool)}
         self._mark('vote+results')
         t0 = tick('vote+results', t0)
-        self.timings = t
         self.last_probs = probs_d
         return fs, result

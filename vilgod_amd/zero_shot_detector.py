@@ -35,7 +35,7 @@ import torch
 
 from . import dist as vdist
 from .boxes import box_method
-from .frame_state import FrameState, pack_clusters, vote
+from .frame_state import FrameState, select_rows_device, sublist_offsets
 from .pipeline import PseudoLabelPipeline
 
 
@@ -249,8 +249,6 @@ class ZeroShotDetector:
 
     def _cluster_lists(self, fnr, rows=None):
         fs = self.lidar_frame_list[fnr]
-        if rows is None:
-            index, seg = fs.index, fs.seg_off
         held = self._dev.get(fnr, {}).get('lists')
         if held is not None and held[0] is fs.index:
             # device.pack=device: the frame's lists never left the GPU (spatial_clustering); a subset of the clusters is cut there too
@@ -258,18 +256,8 @@ class ZeroShotDetector:
                 return held[1], held[2]
             rows = np.asarray(rows, dtype=np.int64)
             if len(rows) and np.all(np.diff(rows) > 0):
-                from .frame_state import select_clusters_device
-                mask = np.zeros(fs.n_detections, np.uint8)
-                mask[rows] = 1
-                o_index, o_seg, _ = select_clusters_device(held[1], held[2], fs.n_detections, torch.from_numpy(mask).to(self.pipe.device),
-                                                           n_index=len(fs.index))
-                return o_index[:int((fs.seg_off[rows + 1] - fs.seg_off[rows]).sum())], o_seg[:len(rows) + 1]
-        if rows is not None:
-            parts = [fs.cluster_index(c) for c in rows]
-            index = np.concatenate(parts) if parts else np.zeros(0, np.int32)
-            seg = np.r_[0, np.cumsum([len(p) for p in parts])].astype(np.int32)
-        dev = self.pipe.device
-        return torch.from_numpy(np.ascontiguousarray(index, dtype=np.int32)).to(dev), torch.from_numpy(seg).to(dev)
+                return select_rows_device(held[1], held[2], fs.n_detections, sublist_offsets(fs.seg_off, rows), rows)
+        return self.pipe.lists_to_device(*((fs.index, fs.seg_off) if rows is None else fs.sublists(rows)))
 
     def _for_frames(self, frames, body, prepare=None, in_order=None):
         """Run `body(pipe, fnr)` for every frame -- sequentially on the caller's stream, or, with device.frames_in_flight > 1,
@@ -610,7 +598,6 @@ class ZeroShotDetector:
         to the frame's points by nearest neighbour.  Either way `Detection.static` comes from the entropy scores when
         they exist (lidar_frame.py:238-243)."""
         from .entropy import TwoFrameClusterer
-        from .frame_state import static_from_entropy
         n_frames = kwargs.get('n_frames', 1)
         force = kwargs.get('force', False)
         two = None
@@ -619,8 +606,6 @@ class ZeroShotDetector:
                 raise RuntimeError(f'spatial_clustering: n_frames={n_frames} but the sequence has {self.lenght} frames')
             dev = self.cfg.get('device', {}) if hasattr(self.cfg, 'get') else {}
             two = TwoFrameClusterer(self.pipe.cluster_model, n_frames=n_frames, seed=int(dev.get('subsample_seed', 0)))
-        ecfg = self.cfg.preprocessor.clustering.get('entropy_score_filter', None) \
-            if hasattr(self.cfg.preprocessor.clustering, 'get') else None
         todo = [f for f in self.my_frames if self.lidar_frame_list[f].ground_point_indices is not None
                 and (self.lidar_frame_list[f].n_detections == 0 or force)]
         X_list, ent_list, parts = [None] * self.lenght, [None] * self.lenght, None
@@ -645,21 +630,13 @@ class ZeroShotDetector:
                 labels, probs = TwoFrameClusterer(p.cluster_model, n_frames=n_frames, seed=seed, parts=parts).labels(fnr, X_list, ent_list)
             else:
                 labels, probs = p.cluster(X)
-            packed = p.pack_device(labels, probs) if getattr(p, 'pack', 'host') == 'device' else None
-            if packed is None:
-                if isinstance(labels, torch.Tensor):
-                    labels, probs = labels.cpu().numpy(), None if probs is None else probs.cpu().numpy()
-                fs.set_clusters(*pack_clusters(labels, probs, p.prob_threshold))     # lidar_frame.py:154-248
-                self._dev[fnr].pop('lists', None)
-            else:
-                fs.set_clusters(*packed[2]())                                        # (the same lists, packed by csrc/pack.hip)
-                self._dev[fnr]['lists'] = (fs.index, packed[0], packed[1])           # read by _cluster_lists while fs.index is this array
+            d_lists, fetch = p.pack_frame(labels, probs)
+            fs.set_clusters(*fetch())                                            # (device.pack=device: the same lists, packed by csrc/pack.hip)
+            self._dev[fnr]['lists'] = d_lists and (fs.index, *d_lists)           # read by _cluster_lists while fs.index is this array
             self._box_prefetch.pop(fnr, None)                                    # (requests sent for the frame's previous clusters)
             ent = self._dev[fnr].get('ent')
             if ent is not None and fs.n_detections:
-                fs.static = static_from_entropy(ent.cpu().numpy(), fs.index, fs.seg_off,
-                                                percentile=float(ecfg['percentile']) if ecfg else 30.0,
-                                                min_percentile_pp_score=float(ecfg['min_percentile_pp_score']) if ecfg else 0.5)
+                fs.static = p.static_flags(ent.cpu().numpy(), fs.index, fs.seg_off)      # lidar_frame.py:238-243
             if 'filter_detections' in fused and fs.n_detections:
                 self._filter_frame(p, fnr)
                 if track_rows is not None:
@@ -702,18 +679,8 @@ class ZeroShotDetector:
         """filter_detections for one frame on pipeline handle `p` (the main one or a worker's)."""
         fs = self.lidar_frame_list[fnr]
         ref, X = self._ref_and_nonground(fnr)
-        if p._filters['use_plane']:
-            gidx = torch.from_numpy(np.asarray(fs.ground_point_indices)).to(p.device)
-            fs.ground_plane_model_ref = p.ground_plane(ref, gidx)             # lidar_frame.py:96-109
-        else:
-            fs.ground_plane_model_ref = np.array([0.0, 0.0, 1.0, 0.0])
-        d_index, d_seg = self._cluster_lists(fnr)
         ent = self._entropy_full(fnr) if p._filters['needs_entropy'] else None      # (None: p.filter raises, naming the stage)
-        valid, _ = p.filter(X, d_index, d_seg, fs.ground_plane_model_ref, entropy=ent)
-        fs.valid = valid.cpu().numpy().astype(bool)
-        if p.last_filter_dict is not None:
-            fs.filter_dict = p.last_filter_dict
-        fs.filtered = True
+        p.plane_and_filter(fs, ref, X, *self._cluster_lists(fnr), entropy=ent)
         self._box_prefetch.pop(fnr, None)                                        # (a request keyed on the previous valid rows)
 
     def filter_detections(self, **kwargs):
@@ -731,7 +698,6 @@ class ZeroShotDetector:
         p = self.pipe
         active = list(self.cfg.pipeline_active)
         return {'key': kwargs.get('key', 'clip'), 'valid_only': kwargs.get('valid_only', False),
-                'names': np.array(p.mapped_names, dtype=object), 'fine_names': np.array(p.class_list, dtype=object),
                 # the static rectangles of the same clusters (box_mode='reference': a helper process per request) are computed while
                 # the GPU encodes the crops; fit_bounding_boxes_simple collects them (they do not depend on the classes)
                 # -- min-area rectangles only: the request carries no method, and an L-shape fit runs on the GPU in the box stage
@@ -753,8 +719,6 @@ class ZeroShotDetector:
 
     def _classify_frame(self, pw, fnr, ctx):
         """classification for one frame on pipeline handle `pw`."""
-        p = self.pipe
-        V = p.projection.num_views
         fs = self.lidar_frame_list[fnr]
         which = fs.valid.copy() if ctx['valid_only'] else np.ones(fs.n_detections, bool)
         rows = np.flatnonzero(which)
@@ -766,11 +730,7 @@ class ZeroShotDetector:
             self._box_prefetch[fnr] = ([int(r) for r in rows], self._fit_rows(fnr, rows, X, wait=False))
         probs, top1, score = pw.classify(X, d_index, d_seg, fs.transform_to_ego)
         self._scores[fnr] = probs
-        fine = top1.cpu().numpy().reshape(len(rows), V)
-        sc = score.cpu().numpy().reshape(len(rows), V).astype(np.float32)
-        mapped = p.fine_to_mapped[fine]
-        win, final = vote(mapped, sc, p.mapped_names)
-        fs.set_classes(ctx['key'], which, ctx['names'][mapped], ctx['fine_names'][fine], sc, ctx['names'][win], final)
+        pw.vote_classes(fs, ctx['key'], which, top1.cpu().numpy(), score.cpu().numpy())
 
     def classification(self, image_size=224, aggregation='voting', **kwargs):
         ctx = self._classification_context(image_size, aggregation, **kwargs)
@@ -844,9 +804,7 @@ class ZeroShotDetector:
         meanwhile).  method: (name, args) of box_method, None = minimum_bounding_rectangle."""
         from .boxes import _Done
         fs = self.lidar_frame_list[fnr]
-        parts = [fs.cluster_index(c) for c in rows]
-        index = np.concatenate(parts).astype(np.int32)
-        seg = np.r_[0, np.cumsum([len(p) for p in parts])].astype(np.int32)
+        index, seg = fs.sublists(rows)
         if method is not None and method[0] != 'minimum_bounding_rectangle':
             boxes = self.pipe.fit_boxes(X, index, seg, method={'name': method[0], 'args': method[1]})
             return boxes if wait else _Done(boxes)
