@@ -206,9 +206,19 @@ int vg_vit_classify_graph(vg_vit* v, vg_graph_cache* c, const void* d_crops, int
                           const float* d_text, int dim, int n_classes, float* d_probs, int32_t* d_top1, float* d_top1_score, void* stream);
 
 /* clip_utils.py:42-61: probs = softmax(100 * normalise(feat) @ text.T) (d_text rows already unit
- * norm, clip_utils.py:26), top-1 class id and probability per crop.  n_classes <= 64. */
+ * norm, clip_utils.py:26), top-1 class id and probability per crop.  One wave per crop, one lane per class: n_classes <= 64
+ * (more is VG_ERR_ARG; vg_clip_scores_wide takes any number). */
 int vg_clip_scores(const float* d_feat, int n, int dim, const float* d_text, int n_classes, float* d_probs,
                    int32_t* d_top1, float* d_top1_score, void* stream);
+/* The same function for a class list of any length (clip_utils.py:22-26 builds one text row per entry of clip.class_list, :43 takes
+ * the softmax over all of them; :49-61 the top-1): d_feat [n, dim], d_text [n_classes, dim], d_probs [n, n_classes], d_top1 /
+ * d_top1_score [n]; the lowest index wins a tie.  Any n_classes >= 1 and any dim; n * n_classes is indexed in 64 bits.  One
+ * 256-thread workgroup per crop; d_probs also holds the crop's logits between the kernel's passes.  A class's logit, probability and
+ * rank do not depend on how many other classes there are, and for n_classes <= 64 the results equal vg_clip_scores' bit for bit.
+ * n <= 0: VG_OK, nothing is launched.  Null pointers or n_classes <= 0: VG_ERR_ARG, nothing is launched.
+ * vg_vit_classify_graph uses vg_clip_scores up to 64 classes and this entry point above. */
+int vg_clip_scores_wide(const float* d_feat, int n, int dim, const float* d_text, int n_classes, float* d_probs,
+                        int32_t* d_top1, float* d_top1_score, void* stream);
 
 /* ---- ground segmentation (rows A1-A5) -----------------------------------------------------------
  * Replaces the pybind11 module `pypatchworkpp` (third_party/patchwork-plusplus/python_wrapper/pybinding.cpp:9-55)

@@ -19,6 +19,7 @@ from . import clip_weights
 from ._lib import lib, ptr, stream_ptr, check
 
 DTYPES = {'f32': 0, 'f16': 1}
+NARROW_CLASSES = 64          # vg_clip_scores' limit (one lane per class); longer class lists go to vg_clip_scores_wide
 
 
 class VitEncoder:
@@ -190,9 +191,28 @@ def clip_scores(feat, text_features, stream=None):
     top1 = torch.empty((n,), dtype=torch.int32, device=feat.device)
     score = torch.empty((n,), dtype=torch.float32, device=feat.device)
     if n:
-        check(lib.vg_clip_scores(ptr(feat), n, dim, ptr(text_features), K, ptr(probs), ptr(top1), ptr(score),
-                                 stream_ptr(stream)), 'vg_clip_scores')
+        # one wave per crop up to its 64 classes, one workgroup per crop above (the same bits where both apply)
+        fn, name = (lib.vg_clip_scores, 'vg_clip_scores') if K <= NARROW_CLASSES else (lib.vg_clip_scores_wide, 'vg_clip_scores_wide')
+        check(fn(ptr(feat), n, dim, ptr(text_features), K, ptr(probs), ptr(top1), ptr(score), stream_ptr(stream)), name)
     return probs, top1, score
+
+
+def validate_class_list(class_list, class_mapping=None):
+    """clip.class_list / clip.class_mapping as the pipeline reads them: every name once, and (where a mapping is given) every name
+    mapped.  Raises ValueError naming the offending classes; returns the list."""
+    class_list = list(class_list)
+    seen, dup = set(), []
+    for c in class_list:
+        if c in seen and c not in dup:
+            dup.append(c)
+        seen.add(c)
+    if dup:
+        raise ValueError(f'clip.class_list names a class more than once: {dup}')
+    if class_mapping is not None:
+        missing = [c for c in class_list if c not in class_mapping]
+        if missing:
+            raise ValueError(f'clip.class_mapping has no entry for these classes of clip.class_list: {missing}')
+    return class_list
 
 
 class ClipWrapper:
@@ -207,7 +227,7 @@ class ClipWrapper:
             raise NotImplementedError('only top_k = 1 (tools/configs/preprocessor/*.yaml) is implemented on the GPU')
         self.split_size = g('split_size', 50)
         self.template = g('prompt_template')
-        class_list = list(g('class_list'))
+        class_list = validate_class_list(g('class_list'), g('class_mapping'))       # before anything is built on the device
         self.id_to_class_dict = {idx: name for idx, name in enumerate(class_list)}
         model_name = str(g('model_name', 'ViT-B-16.pt'))
         tower = clip_weights.tower_config(model_name)        # raises for ViT-L-14-336px.pt; None for a name it does not know
@@ -250,7 +270,8 @@ class ClipWrapper:
 
     def predict_clip_labels(self, crops):
         """crops: [n,3,224,224] CUDA tensor.  Returns (class names, scores) lists of length n, as
-        clip_utils.py:49-63 with top_k = 1."""
+        clip_utils.py:49-63 with top_k = 1.  clip.class_list may have any length (clip_utils.py:22-26, 43): up to 64 classes are
+        scored by vg_clip_scores, longer lists by vg_clip_scores_wide."""
         probs, top1, score = self.predict_probs(crops)
         top1 = top1.cpu().numpy()
         score = score.cpu().numpy()
