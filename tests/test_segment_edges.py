@@ -167,6 +167,34 @@ def test_capacity_circles_have_the_stated_hulls():
         assert len(sr.exact_hull(circle(n)[:, :2])) == n
 
 
+RING_SIZES = (512, 513, 1024, 1025)          # VG_BOX_MAX_HULL and the filter's hull capacity (filters_ref.HULL_CAPACITY), and one more
+
+
+def ring(n, start_first):
+    """circle(n) with its start vertex (lowest y, then lowest x) at the first or the last position of the index list"""
+    p = circle(n)
+    s = int(np.lexsort((p[:, 0], p[:, 1]))[0])
+    rest = np.delete(np.arange(n), s)
+    return p[np.r_[s, rest] if start_first else np.r_[rest, s]]
+
+
+def hull_cases():
+    """The clusters both hull callers (vg_cluster_boxes, vg_cluster_filter_ex) are run on: box_cases() from 3 points up and the rings."""
+    c = {name: p for name, p in box_cases().items() if len(p) >= 3}
+    for n in RING_SIZES:
+        c[f'ring{n}_start_first'], c[f'ring{n}_start_last'] = ring(n, True), ring(n, False)
+    return c
+
+
+def test_capacity_rings_have_the_stated_hulls():
+    for n in RING_SIZES:
+        for first in (True, False):
+            p = ring(n, first)
+            assert len(sr.exact_hull(p[:, :2])) == n
+            low = p[:, 1] == p[:, 1].min()
+            assert low.sum() == 1 and low[0 if first else n - 1]
+
+
 def test_rectangle_reference_agrees_with_the_oracle_on_tie_free_shapes():
     """so.fit_box(all_edges=True) evaluates the reference's float32 expression sequence on qhull's vertices: its box is the float64
     all-edges box within float32 resolution of the coordinates."""
@@ -475,6 +503,50 @@ def test_hip_cluster_boxes_pass_the_property_check(cuda):
     print(f'vg_cluster_boxes: {len(used)} clusters pass; largest share of the bound k = {sr.K_BOX} (8 x k_ref = {sr.K_REF}): '
           f'{used[top]:.3f} (cluster {top}); straddling cluster: {int(aux[names.index("straddle"), 0])} hull vertices')
     assert aux[names.index('lattice'), 0] == 4
+
+
+def _run_area_filter(cuda, clusters):
+    """vg_cluster_filter_ex with only the area filter active (every threshold open) -> stats [C, 16]"""
+    import torch
+    from vilgod_amd._lib import lib, ptr, stream_ptr, check, FilterParams, FILTER_NAMES, FILTER_AND, FILTER_NSTATS
+    X, index, seg = pack(clusters)
+    d_X, d_index, d_seg = (torch.from_numpy(v).to(cuda) for v in (X, index, seg))
+    C = len(clusters)
+    p = FilterParams()
+    p.active[FILTER_NAMES.index('filter_by_area')], p.logic[FILTER_NAMES.index('filter_by_area')] = 1, FILTER_AND
+    stats = torch.full((C, FILTER_NSTATS), -7.0, dtype=torch.float64, device=cuda)
+    verdict = torch.zeros((C, len(FILTER_NAMES)), dtype=torch.uint8, device=cuda)
+    valid = torch.zeros(C, dtype=torch.uint8, device=cuda)
+    check(lib.vg_cluster_filter_ex(ptr(d_X), d_X.stride(0), ptr(d_index), ptr(d_seg), C, ptr(torch.from_numpy(FILTER_PLANE).to(cuda)), None,
+                                   ctypes.byref(p), ptr(stats), ptr(verdict), ptr(valid), stream_ptr()))
+    return stats.cpu().numpy()
+
+
+@pytest.mark.gpu
+def test_hip_box_and_filter_hulls_agree(cuda):
+    """The two callers of vg_hull_wrap (csrc/segment.hip) on the same clusters: where neither overflows, both report the exact hull's
+    vertex count and the same degenerate flag.  Rings at both capacities, start vertex first and last in the index list: a hull of
+    exactly the capacity closes unflagged, one more vertex is flagged and reports the capacity."""
+    from vilgod_amd._lib import (BOX_FLAG_DEGENERATE, BOX_FLAG_HULL_OVERFLOW, BOX_MAX_HULL, FILTER_FLAG_DEGENERATE,
+                                 FILTER_FLAG_HULL_OVERFLOW)
+    import filters_ref as fr
+    cases = hull_cases()
+    names = list(cases)
+    _, aux, _ = _run_boxes(cuda, [cases[n] for n in names])
+    stats = _run_area_filter(cuda, [cases[n] for n in names])
+    seen = set()
+    for c, name in enumerate(names):
+        nh = len(sr.exact_hull(cases[name][:, :2]))
+        flags = int(stats[c, 12])
+        box_over, fil_over = aux[c, 2] == BOX_FLAG_HULL_OVERFLOW, bool(flags & FILTER_FLAG_HULL_OVERFLOW)
+        assert box_over == (nh > BOX_MAX_HULL) and fil_over == (nh > fr.HULL_CAPACITY), (name, nh, aux[c], stats[c, 11:13])
+        assert aux[c, 0] == (BOX_MAX_HULL if box_over else nh), (name, nh, aux[c])
+        assert stats[c, 11] == (fr.HULL_CAPACITY if fil_over else nh), (name, nh, stats[c, 11:13])
+        if not box_over and not fil_over:
+            assert aux[c, 0] == stats[c, 11] == nh, (name, nh, aux[c], stats[c, 11])
+            assert (aux[c, 2] == BOX_FLAG_DEGENERATE) == bool(flags & FILTER_FLAG_DEGENERATE), (name, aux[c], flags)
+        seen.add((nh, bool(box_over), fil_over))
+    assert {(512, False, False), (513, True, False), (1024, True, False), (1025, True, True)} <= seen
 
 
 @pytest.mark.gpu

@@ -70,18 +70,22 @@ def _load():
 
 lib = _load()
 
-# largest min_samples vg_cluster_mst[_nd] takes (include/vilgod_hip.h)
-CLUSTER_MAX_K = int(re.search(r'#define\s+VG_CLUSTER_MAX_K\s+(\d+)', open(HEADER).read()).group(1))
+# the integer `#define VG_*` constants of the header, read once: a missing name is a KeyError at import (a define whose value is
+# not a plain decimal integer -- 0.5, 0x10 -- is absent, never truncated)
+_DEFINES = {m.group(1): int(m.group(2))
+            for m in re.finditer(r'^#define[ \t]+VG_(\w+)[ \t]+(\d+)[ \t]*(?:/\*.*|//.*)?$', open(HEADER).read(), flags=re.M)}
 
+# largest min_samples vg_cluster_mst[_nd] takes
+CLUSTER_MAX_K = _DEFINES['CLUSTER_MAX_K']
 
 # vg_cluster_filter_ex: column order of d_verdict / vg_filter_params.active (include/vilgod_hip.h VG_FILTER_*)
 FILTER_NAMES = ('filter_by_number_points', 'filter_by_height', 'filter_by_aspect_ratio', 'filter_by_volume', 'filter_by_area',
                 'filter_by_plane_distance', 'filter_by_ephemeral_score')
-FILTER_AND_REQUIRED, FILTER_AND, FILTER_OR = 0, 1, 2
-FILTER_NSTATS = 16
-FILTER_FLAG_DEGENERATE, FILTER_FLAG_HULL_OVERFLOW = 1, 2
-BOX_MAX_HULL = 512                                        # vg_cluster_boxes d_aux3 (VG_BOX_*)
-BOX_FLAG_DEGENERATE, BOX_FLAG_HULL_OVERFLOW = 1, 2
+FILTER_AND_REQUIRED, FILTER_AND, FILTER_OR = (_DEFINES['FILTER_' + k] for k in ('AND_REQUIRED', 'AND', 'OR'))
+FILTER_NSTATS = _DEFINES['FILTER_NSTATS']
+FILTER_FLAG_DEGENERATE, FILTER_FLAG_HULL_OVERFLOW = _DEFINES['FILTER_FLAG_DEGENERATE'], _DEFINES['FILTER_FLAG_HULL_OVERFLOW']
+BOX_MAX_HULL = _DEFINES['BOX_MAX_HULL']                   # vg_cluster_boxes d_aux3 (VG_BOX_*)
+BOX_FLAG_DEGENERATE, BOX_FLAG_HULL_OVERFLOW = _DEFINES['BOX_FLAG_DEGENERATE'], _DEFINES['BOX_FLAG_HULL_OVERFLOW']
 
 
 class FilterParams(ctypes.Structure):
@@ -113,8 +117,8 @@ class RenderParams(ctypes.Structure):
         super().__init__(int(resolution), int(depth), float(obj_ratio), float(depth_bias), 1.0 + float(depth_bias))
 
 
-RENDER_RESOLUTION = tuple(int(re.search(rf'#define\s+VG_RENDER_{k}_RESOLUTION\s+(\d+)', open(HEADER).read()).group(1)) for k in ('MIN', 'MAX'))
-RENDER_DEPTH = tuple(int(re.search(rf'#define\s+VG_RENDER_{k}_DEPTH\s+(\d+)', open(HEADER).read()).group(1)) for k in ('MIN', 'MAX'))
+RENDER_RESOLUTION = (_DEFINES['RENDER_MIN_RESOLUTION'], _DEFINES['RENDER_MAX_RESOLUTION'])
+RENDER_DEPTH = (_DEFINES['RENDER_MIN_DEPTH'], _DEFINES['RENDER_MAX_DEPTH'])
 
 
 def ptr(t):

@@ -29,27 +29,6 @@
 
 #define LS_WAVES 4            // angles (waves) per block of k_lshape_score
 
-__device__ __forceinline__ double ls_wave_min(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o));
-    return v;
-}
-__device__ __forceinline__ double ls_wave_max(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
-    return v;
-}
-__device__ __forceinline__ double ls_wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ int ls_wave_isum(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 __device__ __forceinline__ float ls_fma(float a, float b, float c) { return fmaf(a, b, c); }
 __device__ __forceinline__ double ls_fma(double a, double b, double c) { return fma(a, b, c); }
 
@@ -101,8 +80,7 @@ __global__ __launch_bounds__(256) void k_lshape_score(const float* __restrict__ 
             ls_proj(x, y, cs, sn, u, v);
             mnx = u < mnx ? u : mnx; mxx = u > mxx ? u : mxx; mny = v < mny ? v : mny; mxy = v > mxy ? v : mxy;
         }
-        mnx = (T)ls_wave_min((double)mnx); mxx = (T)ls_wave_max((double)mxx);          // (float32 -> float64 -> float32: exact)
-        mny = (T)ls_wave_min((double)mny); mxy = (T)ls_wave_max((double)mxy);
+        mnx = vg_wave_min(mnx); mxx = vg_wave_max(mxx); mny = vg_wave_min(mny); mxy = vg_wave_max(mxy);
         if (CRIT == VG_LSHAPE_CLOSENESS) {
             double acc = 0.0;
             for (int i = lane; i < n; i += WAVE) {
@@ -113,7 +91,7 @@ __global__ __launch_bounds__(256) void k_lshape_score(const float* __restrict__ 
                 beta = beta < delta_zero ? delta_zero : beta;   // np.maximum(beta, delta_zero), float64
                 acc += 1.0 / beta;
             }
-            crit = ls_wave_sum(acc);
+            crit = vg_wave_sum(acc);
         } else {
             int nx = 0, ny = 0;
             double sx = 0.0, sy = 0.0;
@@ -124,8 +102,8 @@ __global__ __launch_bounds__(256) void k_lshape_score(const float* __restrict__ 
                 if (dx < dy) { nx++; sx += dx; }
                 if (dy < dx) { ny++; sy += dy; }
             }
-            nx = ls_wave_isum(nx); ny = ls_wave_isum(ny);
-            sx = ls_wave_sum(sx); sy = ls_wave_sum(sy);
+            nx = vg_wave_sum(nx); ny = vg_wave_sum(ny);
+            sx = vg_wave_sum(sx); sy = vg_wave_sum(sy);
             const double mx = nx > 0 ? sx / (double)nx : 0.0, my = ny > 0 ? sy / (double)ny : 0.0;
             double qx = 0.0, qy = 0.0;
             for (int i = lane; i < n; i += WAVE) {
@@ -135,7 +113,7 @@ __global__ __launch_bounds__(256) void k_lshape_score(const float* __restrict__ 
                 if (dx < dy) { const double e = dx - mx; qx += e * e; }
                 if (dy < dx) { const double e = dy - my; qy += e * e; }
             }
-            qx = ls_wave_sum(qx); qy = ls_wave_sum(qy);
+            qx = vg_wave_sum(qx); qy = vg_wave_sum(qy);
             if (nx > 0) crit += -(qx / (double)nx);
             if (ny > 0) crit += -(qy / (double)ny);
         }
@@ -147,8 +125,8 @@ __global__ __launch_bounds__(256) void k_lshape_score(const float* __restrict__ 
 // min / max of the cluster's projection with (cs, sn), over the whole 256-thread block; every thread returns the result
 template <typename T>
 __device__ void ls_block_extent(const float* __restrict__ pts, int stride, const int* __restrict__ index, int p0, int n, T cs, T sn,
-                                T& mnx, T& mxx, T& mny, T& mxy, double (*red)[4]) {
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+                                T& mnx, T& mxx, T& mny, T& mxy, T (*slot)[4]) {
+    const int tid = threadIdx.x;
     T x, y, u, v;
     ls_point(pts, stride, index, p0, 0, x, y);
     ls_proj(x, y, cs, sn, u, v);
@@ -158,15 +136,11 @@ __device__ void ls_block_extent(const float* __restrict__ pts, int stride, const
         ls_proj(x, y, cs, sn, u, v);
         mnx = u < mnx ? u : mnx; mxx = u > mxx ? u : mxx; mny = v < mny ? v : mny; mxy = v > mxy ? v : mxy;
     }
-    double r0 = ls_wave_min((double)mnx), r1 = ls_wave_max((double)mxx), r2 = ls_wave_min((double)mny), r3 = ls_wave_max((double)mxy);
-    __syncthreads();                                 // (red may still be read after a previous call)
-    if (lane == 0) { red[wv][0] = r0; red[wv][1] = r1; red[wv][2] = r2; red[wv][3] = r3; }
+    __syncthreads();                                 // (the slots may still be read: the z extent, a previous call)
+    vg_block_put(slot[0], vg_wave_min(mnx)); vg_block_put(slot[1], vg_wave_max(mxx));
+    vg_block_put(slot[2], vg_wave_min(mny)); vg_block_put(slot[3], vg_wave_max(mxy));
     __syncthreads();
-    r0 = red[0][0]; r1 = red[0][1]; r2 = red[0][2]; r3 = red[0][3];
-    for (int k = 1; k < 4; ++k) {
-        r0 = fmin(r0, red[k][0]); r1 = fmax(r1, red[k][1]); r2 = fmin(r2, red[k][2]); r3 = fmax(r3, red[k][3]);
-    }
-    mnx = (T)r0; mxx = (T)r1; mny = (T)r2; mxy = (T)r3;
+    mnx = vg_block_min(slot[0]); mxx = vg_block_max(slot[1]); mny = vg_block_min(slot[2]); mxy = vg_block_max(slot[3]);
 }
 
 // box[c] = {cx, cy, cz, l, w, h + 0.3, rz}; aux[c] = {chosen angle index, its criterion, rz before the l/w swap}
@@ -175,8 +149,11 @@ __global__ __launch_bounds__(256) void k_lshape_pick(const float* __restrict__ p
                                                      const int* __restrict__ seg_off, const double* __restrict__ table, int n_angles,
                                                      const double* __restrict__ work, double* __restrict__ box, double* __restrict__ aux) {
     typedef typename std::conditional<CRIT == VG_LSHAPE_CLOSENESS, float, double>::type T;
-    __shared__ double red[4][4];
-    __shared__ int red_i[4];
+    __shared__ union {                               // one phase after the other, a barrier between them
+        struct { double v[4]; int i[4]; } best;
+        float z[2][4];
+        T ext[4][4];
+    } red;
     const int c = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int p0 = seg_off[c], n = seg_off[c + 1] - p0;
     // first index of the maximum: every thread starts from angle 0 and walks its angles upwards with a strict `>`; the threads
@@ -194,11 +171,11 @@ __global__ __launch_bounds__(256) void k_lshape_pick(const float* __restrict__ p
         const int oi = __shfl_xor(bi, o);
         if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
     }
-    if (lane == 0) { red[wv][0] = best; red_i[wv] = bi; }
+    if (lane == 0) { red.best.v[wv] = best; red.best.i[wv] = bi; }
     __syncthreads();
-    best = red[0][0]; bi = red_i[0];
+    best = red.best.v[0]; bi = red.best.i[0];
     for (int k = 1; k < 4; ++k)
-        if (red[k][0] > best || (red[k][0] == best && red_i[k] < bi)) { best = red[k][0]; bi = red_i[k]; }
+        if (red.best.v[k] > best || (red.best.v[k] == best && red.best.i[k] < bi)) { best = red.best.v[k]; bi = red.best.i[k]; }
     if (n == 0) {                                    // nothing to fit: a NaN box (the reference never sees an empty cluster)
         if (tid == 0) {
             const double nan = (double)__int_as_float(0x7fc00000);
@@ -209,25 +186,17 @@ __global__ __launch_bounds__(256) void k_lshape_pick(const float* __restrict__ p
     }
     const double* t = table + (size_t)bi * VG_LSHAPE_TABLE_STRIDE;
     // z extent of the cluster, float32
-    float zmin = pts[(size_t)index[p0] * stride + 2], zmax = zmin;
-    for (int i = tid; i < n; i += 256) {
-        const float z = pts[(size_t)index[p0 + i] * stride + 2];
-        zmin = fminf(zmin, z); zmax = fmaxf(zmax, z);
-    }
-    zmin = vg_wave_min(zmin); zmax = vg_wave_max(zmax);
     __syncthreads();                                 // (red was read above)
-    if (lane == 0) { red[wv][0] = zmin; red[wv][1] = zmax; }
-    __syncthreads();
-    zmin = fminf(fminf((float)red[0][0], (float)red[1][0]), fminf((float)red[2][0], (float)red[3][0]));
-    zmax = fmaxf(fmaxf((float)red[0][1], (float)red[1][1]), fmaxf((float)red[2][1], (float)red[3][1]));
+    const VgExtent e = vg_cluster_extent<1, false>(pts, stride, index + p0, n, nullptr, red.z, nullptr);
+    const float zmin = e.lo[2], zmax = e.hi[2];
     // the projection at the chosen angle; the other orientation when its x extent is the smaller (:206-215, :268-278)
     T cs = (T)t[0], sn = (T)t[1];
     T mnx, mxx, mny, mxy;
-    ls_block_extent(pts, stride, index, p0, n, cs, sn, mnx, mxx, mny, mxy, red);
+    ls_block_extent(pts, stride, index, p0, n, cs, sn, mnx, mxx, mny, mxy, red.ext);
     const bool flip = (T)(mxx - mnx) < (T)(mxy - mny);
     if (flip) {
         cs = (T)t[2]; sn = (T)t[3];
-        ls_block_extent(pts, stride, index, p0, n, cs, sn, mnx, mxx, mny, mxy, red);
+        ls_block_extent(pts, stride, index, p0, n, cs, sn, mnx, mxx, mny, mxy, red.ext);
     }
     // corners: rval @ components, rval = [[max_x, min_y], [min_x, min_y], [min_x, max_y], [max_x, max_y]]
     T c0x, c0y, c1x, c1y, c2x, c2y, c3x, c3y;

@@ -44,31 +44,6 @@ __global__ void k_gather_ego(const float* __restrict__ pts, int stride, const in
 }
 
 // ---------------------------------------------------------------------------------------------
-// k-th smallest (0-based) of the `axis` coordinate over one cluster: 4-pass byte radix select.
-// Called by a 256-thread GROUP of the workgroup (`t` = thread index inside the group) with the group's own hist / sh arrays; every
-// group of the workgroup makes the same number of calls, so the workgroup barriers inside line up.
-__device__ float radix_select(const float* __restrict__ v, int n, int axis, int k, uint32_t* hist,
-                              uint32_t* sh, int t) {
-    uint32_t prefix = 0;
-    for (int pass = 3; pass >= 0; --pass) {
-        hist[t] = 0;
-        __syncthreads();
-        int shift = pass * 8;
-        for (int i = t; i < n; i += 256) {
-            uint32_t key = vg_fkey(v[(size_t)i * 3 + axis]);
-            bool match = (pass == 3) || ((key >> (shift + 8)) == prefix);
-            if (match) atomicAdd(&hist[(key >> shift) & 255u], 1u);
-        }
-        __syncthreads();
-        vg_rank_bin(hist, sh, t, k);
-        __syncthreads();
-        prefix = (prefix << 8) | sh[0];
-        k -= (int)sh[1];
-        __syncthreads();
-    }
-    return vg_fkey_inv(prefix);
-}
-
 // out_rot[0..5] = {m00,m01,m10,m11,m22,angle} of scipy Rotation.from_euler('z', -angle).as_matrix() in float64 for a float32 view
 // angle: scipy converts -angle to float64 and builds the quaternion (0,0,sin(a/2),cos(a/2)), then the matrix from the quaternion.
 __device__ __forceinline__ void view_rotation(float ang, double* __restrict__ out_rot) {
@@ -97,16 +72,9 @@ __global__ __launch_bounds__(768) void k_cluster_median(const float* __restrict_
     const float* v = ego + (size_t)p0 * 3;
     {
         const int a = threadIdx.x >> 8, t = threadIdx.x & 255;
-        float m = 0.f;
-        if (n > 0) {                                                  // n is uniform: every group takes the same branches
-            float hi = radix_select(v, n, a, n / 2, hist[a], sh[a], t);
-            if (n & 1) {
-                m = hi;
-            } else {
-                float lo = radix_select(v, n, a, n / 2 - 1, hist[a], sh[a], t);
-                m = (lo + hi) / 2.0f;  // np.mean of the two middle float32 values
-            }
-        }
+        // n is uniform: every group makes the same calls of the select (common.h), whose workgroup barriers then line up.  One atomic
+        // per key: with the wave-aggregated add this kernel took 540 us per frame instead of 104
+        const float m = n > 0 ? vg_median_select<false>([&](int i) { return vg_fkey(v[(size_t)i * 3 + a]); }, n, hist[a], sh[a], t) : 0.f;
         if (t == 0) med[a] = m;
     }
     __syncthreads();

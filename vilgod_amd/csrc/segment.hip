@@ -78,20 +78,17 @@ __global__ __launch_bounds__(256) void k_plane_hyp(const float* __restrict__ pts
         pl[3] = -((C[0] * P[1][0] + C[1] * P[1][1]) + C[2] * P[1][2]);
     }
     __syncthreads();
-    const double a = pl[0], b = pl[1], c = pl[2], d = pl[3];
-    const double inv = sqrt((a * a + b * b) + c * c);
+    const double plane[4] = {pl[0], pl[1], pl[2], pl[3]};
+    const double inv = vg_plane_norm(plane);
     int local = 0;
     for (int i = part * 256 + threadIdx.x; i < n; i += 256 * nparts) {
         const float* p = pts + (size_t)(idx ? idx[i] : i) * stride;
-        double dist = ((((a * (double)p[0] + b * (double)p[1]) + c * (double)p[2]) + d)) / inv;
-        if (fabs(dist) <= thresh) local++;
+        if (fabs(vg_plane_distance(plane, inv, p)) <= thresh) local++;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) local += __shfl_xor(local, o);
-    if ((threadIdx.x & 63) == 0) cnt[threadIdx.x >> 6] = local;
+    vg_block_put(cnt, vg_wave_sum(local));
     __syncthreads();
     if (threadIdx.x == 0) {
-        atomicAdd(&count_out[it], cnt[0] + cnt[1] + cnt[2] + cnt[3]);
+        atomicAdd(&count_out[it], vg_block_sum(cnt));
         if (part == 0)
             for (int k = 0; k < 4; ++k) plane_out[it * 4 + k] = pl[k];
     }
@@ -112,14 +109,23 @@ __global__ void k_plane_inliers(const float* __restrict__ pts, int stride, const
                                 const double* __restrict__ plane, double thresh, unsigned char* __restrict__ flags) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const double a = plane[0], b = plane[1], c = plane[2], d = plane[3];
-    const double inv = sqrt((a * a + b * b) + c * c);
     const float* p = pts + (size_t)(idx ? idx[i] : i) * stride;
-    double dist = ((((a * (double)p[0] + b * (double)p[1]) + c * (double)p[2]) + d)) / inv;
-    flags[i] = fabs(dist) <= thresh ? 1 : 0;
+    flags[i] = fabs(vg_plane_distance(plane, vg_plane_norm(plane), p)) <= thresh ? 1 : 0;
 }
 
 // ---------------------------------------------------------------------------------------------
+// The three shipped filters from a cluster's point count, float32 height (objects.py:112-114) and plane-distance extremes.
+struct VgShippedVerdicts { bool number_points, height, plane_distance; };
+__device__ __forceinline__ VgShippedVerdicts vg_shipped_verdicts(int n, float height, double dmin, double dmax, int min_points,
+                                                                 int max_points, double min_height, double max_height,
+                                                                 double max_min_height, double min_max_height) {
+    VgShippedVerdicts v;
+    v.number_points = n >= min_points && n <= max_points;                              // cluster_utils.py:14-15
+    v.height = (double)height >= min_height && (double)height <= max_height;           // :48-49
+    v.plane_distance = dmin <= max_min_height && dmax >= min_max_height;               // :58-60
+    return v;
+}
+
 // stats[c] = {n, zmin, zmax, dmin, dmax, height}; valid[c] per the three active, required, `and` filters.
 __global__ __launch_bounds__(256) void k_cluster_filter(const float* __restrict__ pts, int stride,
                                                         const int* __restrict__ index, const int* __restrict__ seg_off,
@@ -127,44 +133,18 @@ __global__ __launch_bounds__(256) void k_cluster_filter(const float* __restrict_
                                                         double max_min_height, double min_max_height, double min_height,
                                                         double max_height, float* __restrict__ stats,
                                                         unsigned char* __restrict__ valid) {
-    __shared__ float rz[8];
-    __shared__ double rd[8];
+    __shared__ float rz[2][4];
+    __shared__ double rd[2][4];
     const int c = blockIdx.x;
     const int p0 = seg_off[c], n = seg_off[c + 1] - p0;
-    const double a = plane[0], b = plane[1], cc = plane[2], d = plane[3];
-    const double inv = sqrt((a * a + b * b) + cc * cc);
-    float zmin = INFINITY, zmax = -INFINITY;
-    double dmin = INFINITY, dmax = -INFINITY;
-    for (int i = threadIdx.x; i < n; i += 256) {
-        const float* p = pts + (size_t)index[p0 + i] * stride;
-        zmin = fminf(zmin, p[2]);
-        zmax = fmaxf(zmax, p[2]);
-        double dist = (((a * (double)p[0] + b * (double)p[1]) + cc * (double)p[2]) + d) / inv;
-        dmin = fmin(dmin, dist);
-        dmax = fmax(dmax, dist);
-    }
-    zmin = vg_wave_min(zmin);
-    zmax = vg_wave_max(zmax);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        dmin = fmin(dmin, __shfl_xor(dmin, o));
-        dmax = fmax(dmax, __shfl_xor(dmax, o));
-    }
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { rz[w] = zmin; rz[4 + w] = zmax; rd[w] = dmin; rd[4 + w] = dmax; }
-    __syncthreads();
+    const VgExtent e = vg_cluster_extent<1, true>(pts, stride, index + p0, n, plane, rz, rd);
     if (threadIdx.x == 0) {
-        for (int k = 1; k < 4; ++k) {
-            rz[0] = fminf(rz[0], rz[k]); rz[4] = fmaxf(rz[4], rz[4 + k]);
-            rd[0] = fmin(rd[0], rd[k]); rd[4] = fmax(rd[4], rd[4 + k]);
-        }
-        const float height = rz[4] - rz[0];                   // objects.py:112-114 (float32)
-        const bool ok_n = n >= min_points && n <= max_points;                        // cluster_utils.py:14-15
-        const bool ok_plane = rd[0] <= max_min_height && rd[4] >= min_max_height;    // :58-60
-        const bool ok_h = (double)height >= min_height && (double)height <= max_height;   // :48-49
-        valid[c] = (ok_n && ok_plane && ok_h) ? 1 : 0;
+        const float height = e.hi[2] - e.lo[2];
+        const VgShippedVerdicts v = vg_shipped_verdicts(n, height, e.dmin, e.dmax, min_points, max_points, min_height, max_height,
+                                                        max_min_height, min_max_height);
+        valid[c] = (v.number_points && v.plane_distance && v.height) ? 1 : 0;
         float* s = stats + (size_t)c * 6;
-        s[0] = (float)n; s[1] = rz[0]; s[2] = rz[4]; s[3] = (float)rd[0]; s[4] = (float)rd[4]; s[5] = height;
+        s[0] = (float)n; s[1] = e.lo[2]; s[2] = e.hi[2]; s[3] = (float)e.dmin; s[4] = (float)e.dmax; s[5] = height;
     }
 }
 
@@ -204,6 +184,117 @@ __device__ __forceinline__ double vg_orient(double ax, double ay, double bx, dou
     return vg_orient_exact(d1, d2, d3, d4, p1, p2);
 }
 
+// true when candidate o replaces the current best b as the next counter-clockwise vertex seen from (cx0, cy0): no point to its
+// right; on a line the farthest, then the lowest position.  The ONLY statement of the rule: thread loop, wave and block combine
+__device__ __forceinline__ bool vg_hull_better(double cx0, double cy0, int bi, double bx, double by, double bd2,
+                                               int oi, double ox, double oy, double od2) {
+    if (oi < 0) return false;
+    if (bi < 0) return true;
+    const double orr = vg_orient(cx0, cy0, bx, by, ox, oy);
+    return orr < 0 || (orr == 0 && (od2 > bd2 || (od2 == bd2 && oi < bi)));
+}
+// true when point o replaces b as the start vertex: lowest y, then lowest x, then lowest position in the list
+__device__ __forceinline__ bool vg_hull_lower(int bi, double bx, double by, int oi, double ox, double oy) {
+    // (`&`, `|`: no branches, so the unrolled start pass keeps its gathers in flight)
+    return (oi >= 0) & ((bi < 0) | (oy < by) | ((oy == by) & ((ox < bx) | ((ox == bx) & (oi < bi)))));
+}
+
+// Convex hull of the xy of one cluster (points pts[idx[i] * stride], i < n) by gift wrapping with exact orientation tests, called
+// by a 256-thread workgroup: counter-clockwise from the start vertex, strict vertices only (duplicates and points inside an edge
+// are none).  hx / hy [CAP] and s are the caller's LDS; s must be free on entry and is free on return (a barrier ends the walk).
+//   n         strict vertices written to hx / hy (<= CAP), uniform over the workgroup
+//   overflow  the hull has more than CAP vertices: hx / hy hold the first CAP from the start vertex, the outline is not closed
+//             (a hull of exactly CAP vertices closes unflagged)
+//   degenerate  fewer than 3 strict vertices: no point, identical or collinear points
+struct VgHullLds { double x[4], y[4], d2[4]; int i[4]; int cur; };      // the four waves' candidates; the vertex the walk stands on
+struct VgHull { int n; bool degenerate, overflow; };
+#define HULL_BATCH 4
+template <int CAP>
+__device__ __forceinline__ VgHull vg_hull_wrap(const float* __restrict__ pts, int stride, const int* __restrict__ idx, int n,
+                                               double* hx, double* hy, VgHullLds& s) {
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    auto px = [&](int i) { return (double)pts[(size_t)idx[i] * stride]; };
+    auto py = [&](int i) { return (double)pts[(size_t)idx[i] * stride + 1]; };
+    VgHull h = {0, false, false};
+    {
+        int bi = -1;
+        double bx = 0, by = 0;
+#pragma unroll 4                                   // (four gathers in flight)
+        for (int i = tid; i < n; i += 256) {
+            const double x = px(i), y = py(i);
+            if (vg_hull_lower(bi, bx, by, i, x, y)) { bi = i; bx = x; by = y; }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const int oi = __shfl_xor(bi, o);
+            const double ox = __shfl_xor(bx, o), oy = __shfl_xor(by, o);
+            if (vg_hull_lower(bi, bx, by, oi, ox, oy)) { bi = oi; bx = ox; by = oy; }
+        }
+        if (lane == 0) { s.i[wv] = bi; s.x[wv] = bx; s.y[wv] = by; }
+        __syncthreads();
+        if (tid == 0) {
+            for (int k = 1; k < 4; ++k)
+                if (vg_hull_lower(bi, bx, by, s.i[k], s.x[k], s.y[k])) { bi = s.i[k]; bx = s.x[k]; by = s.y[k]; }
+            s.cur = bi;
+        }
+        __syncthreads();
+    }
+    const int start = s.cur;
+    const bool none = start < 0;                                           // (no point: nothing to wrap)
+    const double sx0 = none ? 0.0 : px(start), sy0 = none ? 0.0 : py(start);
+    while (!none) {
+        const int cur = s.cur;
+        const double cx0 = px(cur), cy0 = py(cur);
+        // capacity: the vertices so far are the first CAP counter-clockwise from the start, the rest of the outline is missing
+        if (h.n >= CAP) { h.overflow = true; break; }                      // uniform: h.n is counted by every thread, so the exit
+        if (tid == 0) { hx[h.n] = cx0; hy[h.n] = cy0; }                    // never reads a counter that thread 0 is advancing
+        h.n++;
+        int best = -1;
+        double bxx = 0, byy = 0, bd2 = -1;
+        // the gathers of HULL_BATCH points are issued before the first of them is judged: the scan waits on memory, not on arithmetic
+        for (int i0 = tid; i0 < n; i0 += 256 * HULL_BATCH) {
+            double x[HULL_BATCH], y[HULL_BATCH];
+#pragma unroll
+            for (int u = 0; u < HULL_BATCH; ++u) {
+                const int i = i0 + 256 * u < n ? i0 + 256 * u : cur;       // (past the end: the current vertex, which is skipped)
+                x[u] = px(i);
+                y[u] = py(i);
+            }
+#pragma unroll
+            for (int u = 0; u < HULL_BATCH; ++u) {
+                if (x[u] == cx0 && y[u] == cy0) continue;                  // the current vertex itself and its duplicates
+                const double d2 = (x[u] - cx0) * (x[u] - cx0) + (y[u] - cy0) * (y[u] - cy0);
+                if (vg_hull_better(cx0, cy0, best, bxx, byy, bd2, i0 + 256 * u, x[u], y[u], d2)) {
+                    best = i0 + 256 * u; bxx = x[u]; byy = y[u]; bd2 = d2;
+                }
+            }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const int oi = __shfl_xor(best, o);
+            const double ox = __shfl_xor(bxx, o), oy = __shfl_xor(byy, o), od = __shfl_xor(bd2, o);
+            if (vg_hull_better(cx0, cy0, best, bxx, byy, bd2, oi, ox, oy, od)) { best = oi; bxx = ox; byy = oy; bd2 = od; }
+        }
+        __syncthreads();                                                   // every thread has read s.cur
+        if (lane == 0) { s.i[wv] = best; s.x[wv] = bxx; s.y[wv] = byy; s.d2[wv] = bd2; }
+        __syncthreads();
+        if (tid == 0) {
+            for (int k = 1; k < 4; ++k)
+                if (vg_hull_better(cx0, cy0, best, bxx, byy, bd2, s.i[k], s.x[k], s.y[k], s.d2[k])) {
+                    best = s.i[k]; bxx = s.x[k]; byy = s.y[k]; bd2 = s.d2[k];
+                }
+            s.cur = best;
+        }
+        __syncthreads();
+        const int nxt = s.cur;
+        if (nxt < 0) break;                                                // all points coincide: one vertex
+        if (px(nxt) == sx0 && py(nxt) == sy0) break;                       // closed
+    }
+    __syncthreads();                                                       // hx / hy of the last vertex are visible
+    h.degenerate = h.n < 3;
+    return h;
+}
+
 // box[c] = {cx, cy, cz, l, w, h, rz} (float64, ref frame); aux[c] = {n_hull, area, flag}: flag 0 = a rectangle over the whole hull,
 // VG_BOX_FLAG_DEGENERATE = fewer than 3 strict hull vertices (0.1 m square at the mean), VG_BOX_FLAG_HULL_OVERFLOW = the hull has
 // more than BOX_MAX_HULL vertices: NO rectangle is fitted (cx, cy, l, w, rz = NaN; cz, h valid), the caller fits that cluster itself
@@ -212,128 +303,38 @@ __global__ __launch_bounds__(256) void k_cluster_box(const float* __restrict__ p
                                                      double* __restrict__ box, float* __restrict__ aux) {
     __shared__ double hx[BOX_MAX_HULL], hy[BOX_MAX_HULL];
     __shared__ double ang[BOX_MAX_HULL];
-    __shared__ double red_v[4];
-    __shared__ double red_d[4];
-    __shared__ int red_i[4];
-    __shared__ float red_z[8];
-    __shared__ int sh_cur, sh_start;
-    __shared__ double sh_sum[2];
+    __shared__ union { VgHullLds hull; float z[2][4]; } sh;              // the z extent is done before the hull starts
+    double* const red_v = sh.hull.x;                                      // after the hull: two block-reduction slots
+    double* const red_d = sh.hull.y;
     const int c = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int p0 = seg_off[c], n = seg_off[c + 1] - p0;
-#define PX(i) ((double)pts[(size_t)index[p0 + (i)] * stride])
-#define PY(i) ((double)pts[(size_t)index[p0 + (i)] * stride + 1])
-    // z extent + mean xy (degenerate fallback) + start vertex: lowest y, then lowest x
-    float zmin = INFINITY, zmax = -INFINITY;
-    double sx = 0, sy = 0, by = INFINITY, bx = INFINITY;
-    int bi = -1;
-    for (int i = tid; i < n; i += 256) {
-        float z = pts[(size_t)index[p0 + i] * stride + 2];
-        zmin = fminf(zmin, z);
-        zmax = fmaxf(zmax, z);
-        double x = PX(i), y = PY(i);
-        sx += x; sy += y;
-        if (y < by || (y == by && x < bx)) { by = y; bx = x; bi = i; }
-    }
-    zmin = vg_wave_min(zmin);
-    zmax = vg_wave_max(zmax);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        sx += __shfl_xor(sx, o);
-        sy += __shfl_xor(sy, o);
-        double oy = __shfl_xor(by, o), ox = __shfl_xor(bx, o);
-        int oi = __shfl_xor(bi, o);
-        if (oi >= 0 && (bi < 0 || oy < by || (oy == by && (ox < bx || (ox == bx && oi < bi))))) { by = oy; bx = ox; bi = oi; }
-    }
-    if (lane == 0) { red_z[wv] = zmin; red_z[4 + wv] = zmax; red_v[wv] = by; red_d[wv] = bx; red_i[wv] = bi; }
-    __syncthreads();
-    if (tid == 0) {
-        for (int k = 1; k < 4; ++k) {
-            red_z[0] = fminf(red_z[0], red_z[k]);
-            red_z[4] = fmaxf(red_z[4], red_z[4 + k]);
-            if (red_i[k] >= 0 && (red_i[0] < 0 || red_v[k] < red_v[0] || (red_v[k] == red_v[0] && (red_d[k] < red_d[0] ||
-                (red_d[k] == red_d[0] && red_i[k] < red_i[0]))))) { red_v[0] = red_v[k]; red_d[0] = red_d[k]; red_i[0] = red_i[k]; }
-        }
-        sh_start = red_i[0];
-        sh_cur = red_i[0];
-    }
-    // NOTE: sx, sy partial sums are per wave; finish them through shared memory
-    __syncthreads();
-    if (lane == 0) { red_v[wv] = sx; red_d[wv] = sy; }
-    __syncthreads();
-    if (tid == 0) { sh_sum[0] = (red_v[0] + red_v[1]) + (red_v[2] + red_v[3]); sh_sum[1] = (red_d[0] + red_d[1]) + (red_d[2] + red_d[3]); }
-    __syncthreads();
-    zmin = red_z[0];
-    zmax = red_z[4];
-    // ---- gift wrapping (counter-clockwise): next = the point with no other point to its right; farthest on ties ----
-    bool overflow = false;
-    int hn = 0;                       // hull vertices so far: counted by every thread (uniform), so the loop exit never reads a
-                                      // shared counter that thread 0 may already be advancing for the next iteration
-    while (n > 0) {
-        const int cur = sh_cur;
-        const double cx0 = PX(cur), cy0 = PY(cur);
-        if (tid == 0 && hn < BOX_MAX_HULL) { hx[hn] = cx0; hy[hn] = cy0; }
-        hn++;
-        int best = -1;
-        double bxx = 0, byy = 0, bd2 = -1;
-        for (int i = tid; i < n; i += 256) {
-            double x = PX(i), y = PY(i);
-            if (x == cx0 && y == cy0) continue;           // the current vertex itself and its duplicates
-            if (best < 0) { best = i; bxx = x; byy = y; bd2 = (x - cx0) * (x - cx0) + (y - cy0) * (y - cy0); continue; }
-            double o = vg_orient(cx0, cy0, bxx, byy, x, y);
-            double d2 = (x - cx0) * (x - cx0) + (y - cy0) * (y - cy0);
-            if (o < 0 || (o == 0 && d2 > bd2)) { best = i; bxx = x; byy = y; bd2 = d2; }
-        }
-        // combine across the block with the same rule
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            int oi = __shfl_xor(best, o);
-            double ox = __shfl_xor(bxx, o), oy = __shfl_xor(byy, o), od = __shfl_xor(bd2, o);
-            if (oi >= 0) {
-                if (best < 0) { best = oi; bxx = ox; byy = oy; bd2 = od; }
-                else {
-                    double orr = vg_orient(cx0, cy0, bxx, byy, ox, oy);
-                    if (orr < 0 || (orr == 0 && (od > bd2 || (od == bd2 && oi < best)))) { best = oi; bxx = ox; byy = oy; bd2 = od; }
-                }
-            }
-        }
-        __syncthreads();
-        if (lane == 0) { red_i[wv] = best; red_v[wv] = bxx; red_d[wv] = byy; }
-        __syncthreads();
-        if (tid == 0) {
-            int b = red_i[0];
-            double x = red_v[0], y = red_d[0];
-            for (int k = 1; k < 4; ++k) {
-                if (red_i[k] < 0) continue;
-                if (b < 0) { b = red_i[k]; x = red_v[k]; y = red_d[k]; continue; }
-                double orr = vg_orient(cx0, cy0, x, y, red_v[k], red_d[k]);
-                double d2a = (x - cx0) * (x - cx0) + (y - cy0) * (y - cy0);
-                double d2b = (red_v[k] - cx0) * (red_v[k] - cx0) + (red_d[k] - cy0) * (red_d[k] - cy0);
-                if (orr < 0 || (orr == 0 && (d2b > d2a || (d2b == d2a && red_i[k] < b)))) { b = red_i[k]; x = red_v[k]; y = red_d[k]; }
-            }
-            sh_cur = b;
-        }
-        __syncthreads();
-        const int nxt = sh_cur;
-        if (nxt < 0) break;                                               // all points coincide: one vertex
-        if (PX(nxt) == PX(sh_start) && PY(nxt) == PY(sh_start)) break;    // closed
-        // capacity: the vertices so far are the first BOX_MAX_HULL counter-clockwise from the lowest point, the rest of the outline is
-        // missing -- a rectangle over them would cover part of the object, so none is fitted
-        if (hn >= BOX_MAX_HULL) { overflow = true; break; }
-    }
-    const int nh = hn;                                                    // strict hull vertices (<= BOX_MAX_HULL; 1 or 2: degenerate)
+    const int* idx = index + p0;
+    const VgExtent e = vg_cluster_extent<1, false>(pts, stride, idx, n, nullptr, sh.z, nullptr);
+    const float zmin = e.lo[2], zmax = e.hi[2];
+    __syncthreads();                                                      // every thread has read sh.z
     // fewer than 3 strict vertices = collinear or identical input (qhull raises -> the reference falls back to a 0.1 m square); three
-    // or more have area, the orientation test being exact
-    __syncthreads();
+    // or more have area, the orientation test being exact.  Beyond capacity a rectangle over the stored vertices would cover part of
+    // the object, so none is fitted
+    const VgHull hull = vg_hull_wrap<BOX_MAX_HULL>(pts, stride, idx, n, hx, hy, sh.hull);
+    const int nh = hull.n;
     double out[7];
     float n_hull = (float)nh, area = 0.f, deg = 0.f;
     const float height = zmax - zmin;                                   // zero_shot_detector.py:459 (float32)
-    if (overflow) {
+    if (hull.overflow) {
         deg = (float)VG_BOX_FLAG_HULL_OVERFLOW;
         out[0] = out[1] = out[3] = out[4] = out[6] = NAN;
-    } else if (nh < 3) {
+    } else if (hull.degenerate) {
         // pointcloud_utils.py:322-326: 0.1 m square at the mean, rz = 0
         deg = (float)VG_BOX_FLAG_DEGENERATE;
-        double mx = sh_sum[0] / (double)n, my = sh_sum[1] / (double)n;
+        double sx = 0, sy = 0;
+        for (int i = tid; i < n; i += 256) {
+            sx += (double)pts[(size_t)idx[i] * stride];
+            sy += (double)pts[(size_t)idx[i] * stride + 1];
+        }
+        vg_block_put(red_v, vg_wave_sum(sx));
+        vg_block_put(red_d, vg_wave_sum(sy));
+        __syncthreads();
+        double mx = vg_block_sum(red_v) / (double)n, my = vg_block_sum(red_d) / (double)n;
         out[0] = mx; out[1] = my; out[3] = 0.1; out[4] = 0.1; out[6] = 0.0;
         // corners (-.05,-.05),(.05,-.05),(.05,.05),(-.05,.05): l = |c0-c1| = 0.1, w = |c0-c3| = 0.1
     } else {
@@ -364,7 +365,6 @@ __global__ __launch_bounds__(256) void k_cluster_box(const float* __restrict__ p
             double oa = __shfl_xor(barea, o), og = __shfl_xor(bang, o);
             if (oa < barea || (oa == barea && og < bang)) { barea = oa; bang = og; }
         }
-        __syncthreads();
         if (lane == 0) { red_v[wv] = barea; red_d[wv] = bang; }
         __syncthreads();
         barea = red_v[0]; bang = red_d[0];
@@ -396,11 +396,8 @@ __global__ __launch_bounds__(256) void k_cluster_box(const float* __restrict__ p
         for (int k = 0; k < 7; ++k) box[(size_t)c * 7 + k] = out[k];
         aux[c * 3 + 0] = n_hull; aux[c * 3 + 1] = area; aux[c * 3 + 2] = deg;
     }
-#undef PX
-#undef PY
 }
 
-// ---------------------------------------------------------------------------------------------
 // ---------------------------------------------------------------------------------------------
 // entropy (PP) score of a query frame from its neighbour counts; numpy's pairwise summation order
 // (n < 8: left to right; otherwise 8 running partial sums over blocks of 8, combined as a tree, then the tail).
@@ -452,85 +449,36 @@ __global__ void k_subsample_keys(unsigned long long seed, unsigned long long tag
 // Round 4 (the kernel took 3 ms per frame in the entry point's trace: one workgroup per cluster walked its five columns one after the
 // other, every pass gathered the column again from global memory, and the coordinates of one cluster share their leading bytes, so
 // 256 threads added to ONE histogram bin with one LDS atomic each): a workgroup per (cluster, column); the column's keys are staged
-// in LDS once (<= MED_CAP points; larger clusters keep gathering); a wave adds a bin's count once per DISTINCT bin among its 64 keys.
+// in LDS once (<= MED_CAP points; larger clusters keep gathering); the select (common.h) adds to a bin once per wave.
 #define MED_CAP 12288
-__device__ __forceinline__ void vg_hist_add_wave(uint32_t* hist, uint32_t bin, bool active) {
-    unsigned long long todo = __ballot(active);
-    while (todo) {
-        const int leader = __ffsll((long long)todo) - 1;
-        const uint32_t lb = (uint32_t)__builtin_amdgcn_readlane((int)bin, leader);
-        const unsigned long long same = __ballot(active && bin == lb) & todo;
-        if ((int)(threadIdx.x & 63) == leader) atomicAdd(&hist[lb], (uint32_t)__popcll(same));
-        todo &= ~same;
-    }
-}
-
-template <bool STAGED>
-__device__ float vg_select_keys(const float* __restrict__ pts, int stride, int col, const int* __restrict__ idx, const uint32_t* keys,
-                                int n, int k, uint32_t* hist, uint32_t* sh) {
-    uint32_t prefix = 0;
-    const int n64 = (n + 63) & ~63;                    // whole waves run the aggregation (ballots need every lane of the wave)
-    for (int pass = 3; pass >= 0; --pass) {
-        for (int b = threadIdx.x; b < 256; b += blockDim.x) hist[b] = 0;
-        __syncthreads();
-        const int shift = pass * 8;
-        for (int i = threadIdx.x; i < n64; i += blockDim.x) {
-            uint32_t key = 0;
-            if (i < n) key = STAGED ? keys[i] : vg_fkey(pts[(size_t)idx[i] * stride + col]);
-            const bool in = i < n && (pass == 3 || (key >> (shift + 8)) == prefix);
-            vg_hist_add_wave(hist, (key >> shift) & 255u, in);
-        }
-        __syncthreads();
-        vg_rank_bin(hist, sh, threadIdx.x, k);
-        __syncthreads();
-        prefix = (prefix << 8) | sh[0];
-        k -= (int)sh[1];
-        __syncthreads();
-    }
-    return vg_fkey_inv(prefix);
-}
-
 __global__ __launch_bounds__(256) void k_cluster_medians(const float* __restrict__ pts, int stride, int n_cols,
                                                          const int* __restrict__ index, const int* __restrict__ seg_off,
                                                          float* __restrict__ out) {
     __shared__ uint32_t hist[256];
     __shared__ uint32_t sh[6];
     __shared__ uint32_t keys[MED_CAP];
-    const int c = blockIdx.x, col = blockIdx.y;
+    const int c = blockIdx.x, col = blockIdx.y, t = threadIdx.x;
     const int p0 = seg_off[c], n = seg_off[c + 1] - p0;
+    const int* idx = index + p0;
+    const auto gathered = [&](int i) { return vg_fkey(pts[(size_t)idx[i] * stride + col]); };
     float m = 0.f;
-    if (n > 0) {
-        const int* idx = index + p0;
-        if (n <= MED_CAP) {
-            for (int i = threadIdx.x; i < n; i += blockDim.x) keys[i] = vg_fkey(pts[(size_t)idx[i] * stride + col]);
-            __syncthreads();
-            const float hi = vg_select_keys<true>(pts, stride, col, idx, keys, n, n / 2, hist, sh);
-            m = (n & 1) ? hi : (vg_select_keys<true>(pts, stride, col, idx, keys, n, n / 2 - 1, hist, sh) + hi) / 2.0f;
-        } else {
-            const float hi = vg_select_keys<false>(pts, stride, col, idx, keys, n, n / 2, hist, sh);
-            m = (n & 1) ? hi : (vg_select_keys<false>(pts, stride, col, idx, keys, n, n / 2 - 1, hist, sh) + hi) / 2.0f;
-        }
+    if (n > MED_CAP) {
+        m = vg_median_select<true>(gathered, n, hist, sh, t);
+    } else if (n > 0) {
+        for (int i = t; i < n; i += 256) keys[i] = gathered(i);
+        __syncthreads();
+        m = vg_median_select<true>([&](int i) { return keys[i]; }, n, hist, sh, t);
     }
-    if (threadIdx.x == 0) out[(size_t)c * n_cols + col] = m;
+    if (t == 0) out[(size_t)c * n_cols + col] = m;
 }
 
 // ---------------------------------------------------------------------------------------------
 // Every filter of cluster_utils.py with Detection.filter's and / or / required combination (objects.py:158-181).
-// One workgroup per cluster, walking a persistent grid.  Per cluster: one pass for the float32 extents and the plane distances
-// (the arithmetic of k_cluster_filter), gift wrapping with vg_orient for the xy hull (only when area or volume is active), a
-// radix select on the scores (only when the ephemeral filter is active).  The hull's vertices and the select's staged keys share
-// one LDS buffer: the two phases do not overlap.
+// One workgroup per cluster, walking a persistent grid.  Per cluster: the extent pass of k_cluster_filter with x and y added,
+// vg_hull_wrap for the xy hull (only when area or volume is active), a radix select on the scores (only when the ephemeral filter
+// is active).  The hull's vertices and the select's staged keys share one LDS buffer: the two phases do not overlap.
 #define FEX_HULL_CAP 1024
 #define FEX_KEY_CAP 4096
-__device__ __forceinline__ bool vg_hull_better(double cx0, double cy0, int bi, double bx, double by, double bd2,
-                                               int oi, double ox, double oy, double od2) {
-    // true when candidate o replaces the current best b as the next counter-clockwise vertex seen from (cx0, cy0)
-    if (oi < 0) return false;
-    if (bi < 0) return true;
-    const double orr = vg_orient(cx0, cy0, bx, by, ox, oy);
-    return orr < 0 || (orr == 0 && (od2 > bd2 || (od2 == bd2 && oi < bi)));
-}
-
 __global__ __launch_bounds__(256) void k_cluster_filter_ex(const float* __restrict__ pts, int stride,
                                                            const int* __restrict__ index, const int* __restrict__ seg_off,
                                                            int n_clusters, const double* __restrict__ plane,
@@ -540,142 +488,37 @@ __global__ __launch_bounds__(256) void k_cluster_filter_ex(const float* __restri
     __shared__ double buf[2 * FEX_HULL_CAP];            // hx | hy, or FEX_KEY_CAP staged keys
     __shared__ uint32_t hist[256];
     __shared__ uint32_t sel[6];
-    __shared__ float rf[6][4];
-    __shared__ double rd[2][4];
-    __shared__ double red_x[4], red_y[4], red_d2[4];
-    __shared__ int red_i[4];
-    __shared__ int sh_cur, sh_start;
+    __shared__ union { VgHullLds hull; struct { float f[6][4]; double d[2][4]; } ext; } red;   // the extent is done before the hull starts
     double* hx = buf;
     double* hy = buf + FEX_HULL_CAP;
     uint32_t* keys = reinterpret_cast<uint32_t*>(buf);
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const double a = plane[0], b = plane[1], cc = plane[2], d = plane[3];
-    const double inv = sqrt((a * a + b * b) + cc * cc);
+    const int tid = threadIdx.x;
     const bool want_hull = P.active[VG_FILTER_AREA] || P.active[VG_FILTER_VOLUME];
     const bool want_q = P.active[VG_FILTER_EPHEMERAL_SCORE] != 0;
     for (int c = blockIdx.x; c < n_clusters; c += gridDim.x) {
         const int p0 = seg_off[c], n = seg_off[c + 1] - p0;
         const int* idx = index + p0;
-#define PX(i) ((double)pts[(size_t)idx[i] * stride])
-#define PY(i) ((double)pts[(size_t)idx[i] * stride + 1])
-        // ---- pass 1: float32 extents, plane distances, hull start vertex (lowest y, then lowest x, then lowest position) ----
-        float xmin = INFINITY, xmax = -INFINITY, ymin = INFINITY, ymax = -INFINITY, zmin = INFINITY, zmax = -INFINITY;
-        double dmin = INFINITY, dmax = -INFINITY;
-        for (int i = tid; i < n; i += 256) {
-            const float* p = pts + (size_t)idx[i] * stride;
-            xmin = fminf(xmin, p[0]); xmax = fmaxf(xmax, p[0]);
-            ymin = fminf(ymin, p[1]); ymax = fmaxf(ymax, p[1]);
-            zmin = fminf(zmin, p[2]); zmax = fmaxf(zmax, p[2]);
-            double dist = (((a * (double)p[0] + b * (double)p[1]) + cc * (double)p[2]) + d) / inv;
-            dmin = fmin(dmin, dist);
-            dmax = fmax(dmax, dist);
-        }
-        xmin = vg_wave_min(xmin); xmax = vg_wave_max(xmax);
-        ymin = vg_wave_min(ymin); ymax = vg_wave_max(ymax);
-        zmin = vg_wave_min(zmin); zmax = vg_wave_max(zmax);
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            dmin = fmin(dmin, __shfl_xor(dmin, o));
-            dmax = fmax(dmax, __shfl_xor(dmax, o));
-        }
-        if (lane == 0) {
-            rf[0][wv] = xmin; rf[1][wv] = xmax; rf[2][wv] = ymin; rf[3][wv] = ymax; rf[4][wv] = zmin; rf[5][wv] = zmax;
-            rd[0][wv] = dmin; rd[1][wv] = dmax;
-        }
-        __syncthreads();
-        xmin = fminf(fminf(rf[0][0], rf[0][1]), fminf(rf[0][2], rf[0][3]));
-        xmax = fmaxf(fmaxf(rf[1][0], rf[1][1]), fmaxf(rf[1][2], rf[1][3]));
-        ymin = fminf(fminf(rf[2][0], rf[2][1]), fminf(rf[2][2], rf[2][3]));
-        ymax = fmaxf(fmaxf(rf[3][0], rf[3][1]), fmaxf(rf[3][2], rf[3][3]));
-        zmin = fminf(fminf(rf[4][0], rf[4][1]), fminf(rf[4][2], rf[4][3]));
-        zmax = fmaxf(fmaxf(rf[5][0], rf[5][1]), fmaxf(rf[5][2], rf[5][3]));
-        dmin = fmin(fmin(rd[0][0], rd[0][1]), fmin(rd[0][2], rd[0][3]));
-        dmax = fmax(fmax(rd[1][0], rd[1][1]), fmax(rd[1][2], rd[1][3]));
-        const float height = zmax - zmin;                                  // objects.py:112-114 (float32)
+        const VgExtent e = vg_cluster_extent<3, true>(pts, stride, idx, n, plane, red.ext.f, red.ext.d);
+        const float height = e.hi[2] - e.lo[2];
 
-        // ---- convex hull of xy (cluster_utils.py:25-46), counter-clockwise from the lowest point ----
-        int nh = 0;
-        bool degenerate = false, overflow = false;
+        // ---- convex hull of xy (cluster_utils.py:25-46) ----
+        VgHull hull = {0, false, false};
         double area = 0.0, abs_sum = 0.0;
         if (want_hull && n >= 3) {
-            // the lowest-y points all have y == ymin; among them the lowest x, then the first position
-            double bx = INFINITY;
-            int bi = -1;
-            for (int i = tid; i < n; i += 256) {
-                const double x = PX(i);
-                if (PY(i) == (double)ymin && (x < bx || bi < 0)) { bx = x; bi = i; }
-            }
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                const double ox = __shfl_xor(bx, o);
-                const int oi = __shfl_xor(bi, o);
-                if (oi >= 0 && (bi < 0 || ox < bx || (ox == bx && oi < bi))) { bx = ox; bi = oi; }
-            }
-            if (lane == 0) { red_x[wv] = bx; red_i[wv] = bi; }
-            __syncthreads();
-            if (tid == 0) {
-                for (int k = 1; k < 4; ++k)
-                    if (red_i[k] >= 0 && (red_i[0] < 0 || red_x[k] < red_x[0] || (red_x[k] == red_x[0] && red_i[k] < red_i[0]))) {
-                        red_x[0] = red_x[k]; red_i[0] = red_i[k];
-                    }
-                sh_start = red_i[0];
-                sh_cur = red_i[0];
-            }
-            __syncthreads();
-            const int start = sh_start;
-            degenerate = start < 0;                                        // (no finite y: nothing to wrap)
-            const double sx0 = degenerate ? 0.0 : PX(start), sy0 = degenerate ? 0.0 : PY(start);
-            while (!degenerate) {
-                const int cur = sh_cur;
-                const double cx0 = PX(cur), cy0 = PY(cur);
-                if (nh >= FEX_HULL_CAP) { overflow = true; break; }       // uniform: nh is counted by every thread
-                if (tid == 0) { hx[nh] = cx0; hy[nh] = cy0; }
-                nh++;
-                int best = -1;
-                double bxx = 0, byy = 0, bd2 = -1;
-                for (int i = tid; i < n; i += 256) {
-                    const double x = PX(i), y = PY(i);
-                    if (x == cx0 && y == cy0) continue;                    // the current vertex itself and its duplicates
-                    const double d2 = (x - cx0) * (x - cx0) + (y - cy0) * (y - cy0);
-                    if (vg_hull_better(cx0, cy0, best, bxx, byy, bd2, i, x, y, d2)) { best = i; bxx = x; byy = y; bd2 = d2; }
-                }
-#pragma unroll
-                for (int o = 32; o > 0; o >>= 1) {
-                    const int oi = __shfl_xor(best, o);
-                    const double ox = __shfl_xor(bxx, o), oy = __shfl_xor(byy, o), od = __shfl_xor(bd2, o);
-                    if (vg_hull_better(cx0, cy0, best, bxx, byy, bd2, oi, ox, oy, od)) { best = oi; bxx = ox; byy = oy; bd2 = od; }
-                }
-                __syncthreads();                                           // every thread has read sh_cur
-                if (lane == 0) { red_i[wv] = best; red_x[wv] = bxx; red_y[wv] = byy; red_d2[wv] = bd2; }
-                __syncthreads();
-                if (tid == 0) {
-                    int bb = red_i[0];
-                    double x = red_x[0], y = red_y[0], d2 = red_d2[0];
-                    for (int k = 1; k < 4; ++k)
-                        if (vg_hull_better(cx0, cy0, bb, x, y, d2, red_i[k], red_x[k], red_y[k], red_d2[k])) {
-                            bb = red_i[k]; x = red_x[k]; y = red_y[k]; d2 = red_d2[k];
-                        }
-                    sh_cur = bb;
-                }
-                __syncthreads();
-                const int nxt = sh_cur;
-                if (nxt < 0) { degenerate = true; break; }                 // all points coincide
-                if (PX(nxt) == sx0 && PY(nxt) == sy0) break;               // closed
-            }
-            __syncthreads();                                               // hx / hy of the last vertex are visible
-            if (!degenerate && !overflow) {
-                // shoelace in float64 (products of float32 values are exact); every thread computes the same serial sum
+            __syncthreads();                                               // every thread has read red.ext
+            hull = vg_hull_wrap<FEX_HULL_CAP>(pts, stride, idx, n, hx, hy, red.hull);
+            if (hull.n >= 2 && !hull.overflow) {
+                // shoelace in float64 (products of float32 values are exact); every thread computes the same serial sum.  A closed
+                // 2-vertex walk (collinear points) has two edges for abs_sum and an area of exactly 0
                 double a2 = 0.0;
-                for (int i = 0; i < nh; ++i) {
-                    const int j = i + 1 == nh ? 0 : i + 1;
+                for (int i = 0; i < hull.n; ++i) {
+                    const int j = i + 1 == hull.n ? 0 : i + 1;
                     const double t0 = hx[i] * hy[j], t1 = hx[j] * hy[i];
                     a2 += t0 - t1;
                     abs_sum += fabs(t0) + fabs(t1);
                 }
                 area = 0.5 * fabs(a2);
-                if (nh < 3 || !(area > 0.0)) { degenerate = true; area = 0.0; }
-            } else if (degenerate) {
-                area = 0.0;
+                if (!(area > 0.0)) { hull.degenerate = true; area = 0.0; }
             }
         }
         const double volume = area * (double)height;                       // cluster_utils.py:30 (float64 here)
@@ -689,15 +532,17 @@ __global__ __launch_bounds__(256) void k_cluster_filter_ex(const float* __restri
             lo = lo < 0 ? 0 : (lo > n - 1 ? n - 1 : lo);
             const double g = virt - (double)lo;
             const int hi = lo + 1 < n ? lo + 1 : n - 1;
+            const auto gathered = [&](int i) { return vg_fkey(scores[idx[i]]); };
             float va, vb;
             if (n <= FEX_KEY_CAP) {
-                for (int i = tid; i < n; i += 256) keys[i] = vg_fkey(scores[idx[i]]);
+                for (int i = tid; i < n; i += 256) keys[i] = gathered(i);
                 __syncthreads();
-                va = vg_select_keys<true>(scores, 1, 0, idx, keys, n, lo, hist, sel);
-                vb = hi == lo ? va : vg_select_keys<true>(scores, 1, 0, idx, keys, n, hi, hist, sel);
+                const auto staged = [&](int i) { return keys[i]; };
+                va = vg_radix_select<true>(staged, n, lo, hist, sel, tid);
+                vb = hi == lo ? va : vg_radix_select<true>(staged, n, hi, hist, sel, tid);
             } else {
-                va = vg_select_keys<false>(scores, 1, 0, idx, keys, n, lo, hist, sel);
-                vb = hi == lo ? va : vg_select_keys<false>(scores, 1, 0, idx, keys, n, hi, hist, sel);
+                va = vg_radix_select<true>(gathered, n, lo, hist, sel, tid);
+                vb = hi == lo ? va : vg_radix_select<true>(gathered, n, hi, hist, sel, tid);
             }
             const double A = (double)va, B = (double)vb, dd = B - A;
             q = g >= 0.5 ? B - dd * (1.0 - g) : A + dd * g;               // frame_state.static_from_entropy
@@ -705,16 +550,18 @@ __global__ __launch_bounds__(256) void k_cluster_filter_ex(const float* __restri
 
         if (tid == 0) {
             unsigned char v[VG_FILTER_COUNT];
-            v[VG_FILTER_NUMBER_POINTS] = n >= P.min_points && n <= P.max_points;                          // cluster_utils.py:14-15
-            v[VG_FILTER_HEIGHT] = (double)height >= P.min_height && (double)height <= P.max_height;        // :48-49
-            v[VG_FILTER_PLANE_DISTANCE] = dmin <= P.max_min_height && dmax >= P.min_max_height;            // :58-60
-            const float sx = xmax - xmin, sy = ymax - ymin;                                                // :18 (float32)
+            const VgShippedVerdicts sv = vg_shipped_verdicts(n, height, e.dmin, e.dmax, P.min_points, P.max_points, P.min_height,
+                                                             P.max_height, P.max_min_height, P.min_max_height);
+            v[VG_FILTER_NUMBER_POINTS] = sv.number_points;
+            v[VG_FILTER_HEIGHT] = sv.height;
+            v[VG_FILTER_PLANE_DISTANCE] = sv.plane_distance;
+            const float sx = e.hi[0] - e.lo[0], sy = e.hi[1] - e.lo[1];                                    // :18 (float32)
             const float ratio = fmaxf(sx, sy) / fminf(sx, sy);                                             // :20 (x/0 = inf, 0/0 = nan)
             v[VG_FILTER_ASPECT_RATIO] = (((double)ratio >= P.min_aspect_ratio) || sx < 1.0f || sy < 1.0f) &&
                                         ((double)ratio <= P.max_aspect_ratio);                             // :20-23
-            bool okv = n >= 3 && !overflow && volume >= P.min_volume;                                      // :26-34
+            bool okv = n >= 3 && !hull.overflow && volume >= P.min_volume;                                 // :26-34
             if (P.has_max_volume) okv = okv && volume <= P.max_volume;
-            bool oka = n >= 3 && !overflow && area >= P.min_area;                                          // :37-46
+            bool oka = n >= 3 && !hull.overflow && area >= P.min_area;                                     // :37-46
             if (P.has_max_area) oka = oka && area <= P.max_area;
             v[VG_FILTER_VOLUME] = okv;
             v[VG_FILTER_AREA] = oka;
@@ -730,14 +577,12 @@ __global__ __launch_bounds__(256) void k_cluster_filter_ex(const float* __restri
             for (int k = 0; k < VG_FILTER_COUNT; ++k) verdict[(size_t)c * VG_FILTER_COUNT + k] = v[k];
             valid[c] = ((all_and || any_or) && all_req) ? 1 : 0;
             double* s = stats + (size_t)c * VG_FILTER_NSTATS;
-            s[0] = (double)n; s[1] = (double)zmin; s[2] = (double)zmax; s[3] = dmin; s[4] = dmax; s[5] = (double)height;
-            s[6] = (double)sx; s[7] = (double)sy; s[8] = (double)ratio; s[9] = area; s[10] = volume; s[11] = (double)nh;
-            s[12] = (double)((degenerate ? VG_FILTER_FLAG_DEGENERATE : 0) | (overflow ? VG_FILTER_FLAG_HULL_OVERFLOW : 0));
+            s[0] = (double)n; s[1] = (double)e.lo[2]; s[2] = (double)e.hi[2]; s[3] = e.dmin; s[4] = e.dmax; s[5] = (double)height;
+            s[6] = (double)sx; s[7] = (double)sy; s[8] = (double)ratio; s[9] = area; s[10] = volume; s[11] = (double)hull.n;
+            s[12] = (double)((hull.degenerate ? VG_FILTER_FLAG_DEGENERATE : 0) | (hull.overflow ? VG_FILTER_FLAG_HULL_OVERFLOW : 0));
             s[13] = q; s[14] = abs_sum; s[15] = 0.0;
         }
         __syncthreads();                                                   // the next cluster reuses every shared array
-#undef PX
-#undef PY
     }
 }
 
