@@ -98,6 +98,24 @@ def test_new_core_distance_kernels_use_no_scratch():
     assert build.check_scratch('cluster.hip', 'k_cl_core_blk') == [] and build.check_scratch('cluster.hip', 'k_cl_core_far') == []
 
 
+def test_product_library_holds_one_walk_per_dim_and_no_development_kernel():
+    from vilgod_amd import build
+    text = build._device_asm('cluster.hip')
+    vgprs = {n: int(v) for n, v in re.findall(r'\.set (\S+)\.num_vgpr, (\d+)', text)}
+    kernels = {n for n in vgprs if 'k_cl_' in n}
+    assert len(kernels) >= 40, sorted(kernels)                       # the names were found at all
+    # the Boruvka walk: DIM 3, 4, 5 in workgroups of 512 threads, nothing else (mangled: k_cl_b_searchILi<DIM>ELi<NT>E...)
+    walks = {n for n in kernels if re.match(r'_Z\d+k_cl_b_searchI', n)}
+    assert sorted(re.match(r'_Z\d+k_cl_b_searchI(.*?)Ev', n).group(1) for n in walks) == ['Li3ELi512E', 'Li4ELi512E', 'Li5ELi512E'], walks
+    # a 512-thread workgroup is two waves per SIMD: 256 registers each
+    print({n: vgprs[n] for n in sorted(walks)})
+    assert all(vgprs[n] <= 256 for n in walks), {n: vgprs[n] for n in walks}
+    # what the development build alone has: the cooperative search that was retired, the per-point k-NN walk (k_cl_core itself, not
+    # k_cl_core_blk / k_cl_core_far), the seeding simulation
+    assert not [n for n in kernels if re.match(r'_Z\d+(k_cl_b_search_blk|k_cl_coreI|k_cl_seedsim_drop)', n)]
+    assert build.check_scratch('cluster.hip', 'k_cl_') == []
+
+
 # ------------------------------------------------------------------------------------------- GPU
 def _model(cuda, n, mcs=15, k=None, hierarchy='host'):
     from vilgod_amd.hdbscan import HDBSCAN

@@ -2,21 +2,25 @@
 //
 // Replaces the work hidden in `cluster_model.fit(points_ref_wo_ground)` (src/vilgod/zero_shot_detector.py:248;
 // hdbscan.HDBSCAN(min_cluster_size=15, cluster_selection_epsilon=0.15), tools/configs/preprocessor/waymo.yaml:10-15):
-//   K2a  k_cl_bbox / k_cl_codes / radix sort / k_cl_cell_marks + scan
-//        points -> 0.4 m cells, Morton order (6 interleaved bits + 3 high bits of x,y), dense cell-start table
-//        (any 2^l-aligned cube of cells is ONE contiguous range of the sorted points)
-//   K2b  k_cl_core        exact k-NN core distance: pruned depth-first walk of the implicit octree (nearest child
-//                         first, box-distance pruning against the current k-th distance, nodes with <= 48 points
-//                         scanned directly), float64 distances, 16-entry register-resident sorted list (k <= 15; for
-//                         16 <= k <= VG_CLUSTER_MAX_K see ClLdsHeap and the WIDE form of k_cl_core_far)
-//   K2c  k_cl_b_*         exact minimum spanning tree of the mutual-reachability graph, Boruvka rounds with the
-//                         same walk ("nearest point of another component"): subtrees owned entirely by the
+//   K2a  k_cl_bbox / k_cl_grid / k_cl_codes / radix sort / k_cl_gather + min-scan / k_cl_levels
+//        points -> 0.4 m cells, Morton order (6 interleaved bits + 3 high bits of x,y), dense cell-start table and the same
+//        table per coarser level (any 2^l-aligned cube of cells is ONE contiguous range of the sorted points)
+//   K2b  k_cl_blocks, k_cl_core_blk, k_cl_core_far
+//                         exact k-NN core distance in two cooperative phases over a work list of (octree node, 64 queries)
+//                         items: A scans the 27 nodes around the item from LDS, lane = query; B finishes the queries whose
+//                         k-th distance reaches past that shell, one wave per query, lane = candidate.  float64 distances;
+//                         the k smallest live in registers for k <= 15 and in an LDS heap / across the wave's lanes for
+//                         16 <= k <= VG_CLUSTER_MAX_K (see the comment in front of CLB_ORDER)
+//   K2c  k_cl_b_*         exact minimum spanning tree of the mutual-reachability graph, Boruvka rounds over a pruned depth-first
+//                         walk of the implicit octree ("nearest point of another component", nearest child first, box-distance
+//                         pruning, nodes with <= CL_LEAF points scanned directly): subtrees owned entirely by the
 //                         query's component are skipped through per-round purity tables (levels 0..3), and
 //                         per-component upper bounds published with atomicMin prune the rest of the component;
 //                         edges are ordered by the STRICT total order
 //                         (w2, pair d2, min id, max id) so the tree is unique and equals the oracle's
-//        radix sort of the n-1 edges by weight
-// The sequential hierarchy stage (K2d) is csrc/hdbscan_tree.cpp on the host.
+//        radix sort of the n - 1 edges by weight
+// The hierarchy stage (K2d) takes the sorted edges from here: csrc/hdbscan_device.hip on the device, csrc/hdbscan_tree.cpp on the host.
+// The development build adds dev/cluster_dev.inc: the per-point k-NN walk the cooperative phases replaced, and the A/B switches.
 //
 // All distances are float64 with d2 = (dx*dx + dy*dy) + dz*dz on exactly converted float32 coordinates
 // (what the library computes after its float64 conversion); compiled with -ffp-contract=off.
@@ -24,8 +28,8 @@
 #include <vector>
 #include <algorithm>
 #include <cstring>
+#include <type_traits>
 #include <math.h>
-#include <algorithm>
 #include "common.h"
 #include "vilgod_hip.h"
 #include <rocprim/rocprim.hpp>
@@ -41,7 +45,7 @@
 #ifndef CL_LEAF
 #define CL_LEAF 48                    // nodes with at most this many points are scanned instead of subdivided
 #endif
-#define CL_FIRST_BATCH 6      // Boruvka rounds queued before the first host read of the edge counter (development build: VG_CLUSTER_FIRST_BATCH)
+#define CL_FIRST_BATCH 6      // Boruvka rounds queued before the first host read of the edge counter
 #define CL_STACK 44      // DFS stack entries per thread (LDS): the walk never holds more than 1 + 7 * CL_LMAX = 43 nodes (a pop precedes every push of
                          // <= 8 children, level-0 nodes are never expanded); 44 KB per 256-thread block -> three blocks per CU instead of two
 #define CL_K 16                       // neighbours kept (k-th other point = entry k, entry 0 is the point itself)
@@ -67,25 +71,26 @@ struct vg_cluster {
     int* d_cell_comp;                     // purity tables, levels 0..3 back to back: component id if pure, else -1
     unsigned int* d_cell_e;               // same layout: (min, max) of the 4th coordinate in the node as two fp16 (dim >= 4)
     double* d_core2;                      // [n] sorted order
-    int *d_comp, *d_parent, *d_parent2;   // Boruvka components (sorted index space)
-    unsigned long long *d_best_w, *d_best_e;
-    int *d_sel_a, *d_sel_b;
-    unsigned long long *d_pt_w, *d_pt_key, *d_pt_d, *d_best_d;   // pt_d / best_d: squared pair distance (tie-break after w)
+    int *d_comp, *d_parent2;              // Boruvka: component (= root) of every point; this round's hook of every root (sorted index space)
+    unsigned long long *d_best_w, *d_best_e;   // per component: lightest weight found this round (also the bound the walks prune with); its id key
+    int *d_sel_a, *d_sel_b;               // per component: the two ends of the edge it picked (sel_a = -1: none)
+    unsigned long long *d_pt_w, *d_pt_key, *d_pt_d, *d_best_d;   // per point: its candidate edge (weight, id key, squared pair distance: the tie-break after w); best_d: per component
     int4* d_aux;                          // per sorted point {core2 (2 words), component, 5th coordinate}: what a leaf scan needs next to spts
     double* d_pt_lb;                      // per point: a lower bound of the weight of ANY edge leaving its component (grows over the rounds)
-    int* d_pt_b;
-    int* d_counter;                       // [0] number of MST edges emitted
+    int* d_pt_b;                          // per point: the other end of its candidate edge, -1: none (kept over the rounds while it stays foreign: k_cl_b_seed)
+    int* d_counter;                       // [0] MST edges emitted (| CL_CYCLE), [1] tree complete, [2] work items of the cooperative phases, [3] queries left to
+                                          // k_cl_core_far, [5] development build (SEEDSIM)
     int *d_mst_a, *d_mst_b;               // original ids
-    unsigned long long *d_mst_w, *d_mst_w_s;
-    int *d_mst_idx, *d_mst_idx_s;
-    void* d_temp;
+    unsigned long long *d_mst_w, *d_mst_w_s;   // edge weights as emitted / sorted
+    int *d_mst_idx, *d_mst_idx_s;         // edge numbers, carried through the sort
+    void* d_temp;                         // rocprim scratch (sorts, scan)
     size_t temp_bytes;
-    int* h_counter;                       // pinned
-    int* d_dbg;                           // VG_CLUSTER_DEBUG=1: points scanned per thread in the last search round
-    unsigned int* d_entries;
+    int* h_counter;                       // pinned: the edge count after each of up to 16 queued rounds
+    int* d_dbg;                           // VG_CLUSTER_DEBUG=1 [max_points]: points scanned per query by the core-distance phases / the last search round
+    unsigned int* d_entries;              // work list of the cooperative phases (k_cl_blocks)
     int* d_csize;                          // points per component, kept at the component's root (sorted index space)
     unsigned long long* d_giant;           // this round's largest component: size << 32 | root (0 until the first round's kernels ran)
-    int *d_far, *d_far_flag;  // cooperative kernels: (node, 64-query) work list of the frame; queries handed on to the next phase
+    int* d_far;                            // the queries k_cl_core_blk hands on to k_cl_core_far
 };
 
 // Consecutive hardware workgroup ids are dealt round-robin to the 8 XCDs (observed placement, speed only): logical block = a contiguous run
@@ -115,11 +120,23 @@ __host__ __device__ __forceinline__ unsigned int cl_code(int cx, int cy, int cz)
 // same real number, so every level computes the same faces.  Cells are assigned by these faces, not by the floor alone: the floor of
 // (v - o) * 2.5 puts a coordinate that sits on or next to a face into the neighbouring cell for some origins (ox = -10.4, x = 62.0:
 // floor gives cell 181, whose computed min face is 62.00000000000001), and a box that does not hold its own points is no lower bound.
+__host__ __device__ __forceinline__ double cl_face(double o, int i, int l) {       // face i of level l: the ONLY place that computes one
+    return o + (double)i * (CL_CELL * (double)(1 << l));
+}
+// distance along one axis from q to node c of level l (nb nodes on the axis): 0 inside [lo, hi]; a face the grid clips does not count
+// (border nodes extend to infinity on the outside: points beyond the grid are clamped INTO border cells)
+__host__ __device__ __forceinline__ double cl_axis_gap(double o, double q, int c, int l, int nb) {
+    const double lo = cl_face(o, c, l), hi = cl_face(o, c + 1, l);                 // (lo + size is not a face)
+    double d = 0.0;
+    if (q < lo && c > 0) d = lo - q;
+    else if (q > hi && c < nb - 1) d = q - hi;
+    return d;
+}
 __host__ __device__ __forceinline__ int cl_cell_axis(double o, double v, int n) {
     int c = (int)floor((v - o) * (1.0 / CL_CELL));
     c = c < 0 ? 0 : (c > n - 1 ? n - 1 : c);
-    if (c > 0 && v < o + (double)c * CL_CELL) --c;                          // the floor is at most one cell off (errors ~1e-13 m)
-    else if (c < n - 1 && v >= o + (double)(c + 1) * CL_CELL) ++c;
+    if (c > 0 && v < cl_face(o, c, 0)) --c;                                 // the floor is at most one cell off (errors ~1e-13 m)
+    else if (c < n - 1 && v >= cl_face(o, c + 1, 0)) ++c;
     return c;
 }
 __host__ __device__ __forceinline__ void cl_cell_of(const ClGrid& g, double x, double y, double z, int& cx, int& cy, int& cz) {
@@ -241,7 +258,6 @@ __device__ __forceinline__ double cl_d2(double ax, double ay, double az, double 
 // squared distance from q to the nearest face of the level-l block [b-1, b+2) (faces clipped by the grid do not count)
 __host__ __device__ __forceinline__ double cl_block_radius2(const ClGrid& g, double qx, double qy, double qz, int bx, int by,
                                                    int bz, int l) {
-    const double s = CL_CELL * (double)(1 << l);
     double r = INFINITY;
     const int nb[3] = {CL_NX >> l, CL_NY >> l, CL_NZ >> l};
     const int b[3] = {bx, by, bz};
@@ -249,8 +265,8 @@ __host__ __device__ __forceinline__ double cl_block_radius2(const ClGrid& g, dou
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
         // a face only bounds the search if cells exist beyond it (points outside the grid are clamped INTO border cells)
-        if (b[a] - 2 >= 0) r = fmin(r, q[a] - (o[a] + (double)(b[a] - 1) * s));
-        if (b[a] + 2 < nb[a]) r = fmin(r, (o[a] + (double)(b[a] + 2) * s) - q[a]);
+        if (b[a] - 2 >= 0) r = fmin(r, q[a] - cl_face(o[a], b[a] - 1, l));
+        if (b[a] + 2 < nb[a]) r = fmin(r, cl_face(o[a], b[a] + 2, l) - q[a]);
     }
     if (r < 0) r = 0;
     return isinf(r) ? INFINITY : r * r;
@@ -269,17 +285,13 @@ __device__ __forceinline__ void cl_unpack(unsigned int e, int& l, int& x, int& y
 // squared distance from q to the axis-aligned box of node (l,x,y,z); 0 inside.  Border nodes extend to infinity on
 // the outside (points beyond the grid are clamped INTO border cells).
 __host__ __device__ __forceinline__ double cl_box_d2(const ClGrid& g, double qx, double qy, double qz, int l, int x, int y, int z) {
-    const double s = CL_CELL * (double)(1 << l);
     const int nb[3] = {CL_NX >> l, CL_NY >> l, CL_NZ >> l};
     const int c[3] = {x, y, z};
     const double q[3] = {qx, qy, qz}, o[3] = {g.ox, g.oy, g.oz};
     double d2 = 0.0;
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
-        const double lo = o[a] + (double)c[a] * s, hi = o[a] + (double)(c[a] + 1) * s;      // the faces cl_cell_axis assigns by (lo + s is not one)
-        double d = 0.0;
-        if (q[a] < lo && c[a] > 0) d = lo - q[a];
-        else if (q[a] > hi && c[a] < nb[a] - 1) d = q[a] - hi;
+        const double d = cl_axis_gap(o[a], q[a], c[a], l, nb[a]);
         d2 += d * d;
     }
     return d2;
@@ -347,93 +359,9 @@ __global__ void k_cl_e_up(int n, int l, const unsigned int* __restrict__ code_s,
     cell_e[cl_pur_off_fwd(l) + key] = cl_pack_e(mn, mx);
 }
 
-#ifdef VG_DEV      // the per-point tree walk of rounds 1-2 (superseded by the cooperative kernels below in round 3): A/B aid, development build only
-template <int DIM>
-__global__ __launch_bounds__(256) void k_cl_core(const float4* __restrict__ spts, const float* __restrict__ stt, int n,
-                                                 const ClGrid* __restrict__ gp, const int* __restrict__ cs,
-                                                 const unsigned int* __restrict__ cell_e, int k,
-                                                 double* __restrict__ core2, int* __restrict__ dbg_scan) {
-    __shared__ unsigned int stack[CL_STACK * 256];
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    int scanned = 0;                                  // VG_CLUSTER_DEBUG: pair distances evaluated by this point
-    unsigned int* st = stack + threadIdx.x;
-    const ClGrid g = *gp;
-    const float4 qf = spts[i];
-    const double qx = qf.x, qy = qf.y, qz = qf.z, qe = qf.w, qt = DIM >= 5 ? (double)stt[i] : 0.0;
-    int cx, cy, cz;
-    cl_cell_of(g, qx, qy, qz, cx, cy, cz);
-    double h[CL_K];
-#pragma unroll
-    for (int j = 0; j < CL_K; ++j) h[j] = INFINITY;
-    const int rx0 = cx >> CL_LMAX, ry0 = cy >> CL_LMAX;
-    const int nrx = CL_NX >> CL_LMAX, nry = CL_NY >> CL_LMAX;
-    for (int rr = 0; rr < nrx * nry; ++rr) {
-        // own root first, then the others (pruned by distance)
-        int rx = rr % nrx, ry = rr / nrx;
-        if (rr == 0) { rx = rx0; ry = ry0; }
-        else if (rx == rx0 && ry == ry0) { rx = 0; ry = 0; }
-        int sp = 0;
-        st[0] = cl_pack(CL_LMAX, rx, ry, 0);
-        sp = 1;
-        while (sp > 0) {
-            int l, x, y, z;
-            cl_unpack(st[(--sp) * 256], l, x, y, z);
-            const double nb2 = cl_box_d2(g, qx, qy, qz, l, x, y, z);
-            if (nb2 >= h[k]) continue;                                       // cannot lower the k-th distance (ALU only)
-            const unsigned int c0 = cl_code(x << l, y << l, z << l);
-            const int j0 = cl_start_l(cs, l, c0 >> (3 * l)), j1 = cl_start_l(cs, l, (c0 >> (3 * l)) + 1u);
-            if (j0 == j1) continue;
-            if (DIM >= 4 && l < CL_PUR_LEVELS && nb2 + cl_e_gap2(cell_e[cl_pur_off_fwd(l) + (c0 >> (3 * l))], qe) >= h[k]) continue;
-            if (l == 0 || j1 - j0 <= CL_LEAF) {
-                scanned += j1 - j0;
-                for (int jb = j0; jb < j1; jb += 4) {                       // four independent loads per trip
-                    float4 pj[4];
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) pj[u] = spts[jb + u < j1 ? jb + u : j1 - 1];
-#pragma unroll
-                    for (int v = 0; v < 4; ++v) {
-                        const int j = jb + v;
-                        if (j >= j1) continue;
-                        double d2 = cl_d2<DIM>(qx, qy, qz, qe, qt, pj[v], stt, j);
-                        if (d2 < h[CL_K - 1]) {
-#pragma unroll
-                            for (int u = 0; u < CL_K; ++u)
-                                if (d2 < h[u]) { double tmp = h[u]; h[u] = d2; d2 = tmp; }
-                        }
-                    }
-                }
-                continue;
-            }
-            // children, nearest octant LAST on the stack -> popped first
-            const int l1 = l - 1;
-            const int ox = ((cx >> l1) > 2 * x) ? 1 : 0, oy = ((cy >> l1) > 2 * y) ? 1 : 0, oz = ((cz >> l1) > 2 * z) ? 1 : 0;
-            const int near = ox | (oy << 1) | (oz << 2);
-            // the 8 children are consecutive Morton ranges: their 9 boundaries are loaded together (independent loads), so
-            // empty octants -- most of them in LiDAR data -- are never pushed and never cost a pop with two dependent loads
-            int bnd[9];
-#pragma unroll
-            for (int c = 0; c < 9; ++c) bnd[c] = cl_start_l(cs, l1, (c0 >> (3 * l1)) + (unsigned int)c);
-            unsigned int occupied = 0;                    // bit c: child c holds points (static indices only: no scratch)
-#pragma unroll
-            for (int c = 0; c < 8; ++c) occupied |= (bnd[c] != bnd[c + 1]) ? (1u << c) : 0u;
-            for (int c = 7; c >= 0; --c) {
-                const int ch = c ^ near;
-                if (!((occupied >> ch) & 1u)) continue;
-                const int nx = 2 * x + (ch & 1), ny = 2 * y + ((ch >> 1) & 1), nz = 2 * z + ((ch >> 2) & 1);
-                if (cl_box_d2(g, qx, qy, qz, l1, nx, ny, nz) >= h[k]) continue;
-                if (sp < CL_STACK) st[(sp++) * 256] = cl_pack(l1, nx, ny, nz);
-            }
-        }
-    }
-    core2[i] = h[k];
-    if (dbg_scan) dbg_scan[i] = scanned;
-}
-#endif  // VG_DEV
-
 // ---------------------------------------------------------------------------------------------
 // Cooperative exact k-NN core distances (north_star: "LDS-staged radius-neighbour / HDBSCAN core-distance kernel over
-// Morton-sorted points with coalesced HBM reads").  Two phases, both exact, both bit-identical to the walk above (the same
+// Morton-sorted points with coalesced HBM reads").  Two phases, both exact, both bit-identical to the per-point walk they replaced (k_cl_core, dev/cluster_dev.inc: the same
 // float64 pair distances; the k-th smallest value does not depend on the order in which the pairs are met):
 //   A  k_cl_core_blk   one WAVE per (0.8 m block, 64 queries): the queries of a level-1 node are 64 consecutive sorted points,
 //                      lane = query.  The 27 neighbouring level-1 nodes are 27 contiguous ranges of the sorted array: they are
@@ -759,7 +687,7 @@ template <int DIM, bool WIDE>
 __global__ __launch_bounds__(64) void k_cl_core_far(const float4* __restrict__ spts, const float* __restrict__ stt, int n,
                                                     const ClGrid* __restrict__ gp, const int* __restrict__ cs,
                                                     const int* __restrict__ far_list, const int* __restrict__ counters, int k,
-                                                    double* __restrict__ core2, int* __restrict__ dbg_scan, int force_level) {
+                                                    double* __restrict__ core2, int* __restrict__ dbg_scan) {
     const int lane = threadIdx.x;
     const ClGrid g = *gp;
     const int n_far = counters[3];
@@ -773,7 +701,6 @@ __global__ __launch_bounds__(64) void k_cl_core_far(const float4* __restrict__ s
         int L = 2;
         while (L < CL_LMAX && !(bound <= cl_block_radius2(g, qx, qy, qz, cx >> L, cy >> L, cz >> L, L))) ++L;
         if (isinf(bound)) L = 3;
-        if (force_level) L = force_level;
         const int kl = WIDE ? k - 1 : k;                  // the lane that holds the answer
         double hs = g.inf;                                // lane r: the r-th smallest distance so far (WIDE: the (r + 1)-th to another point)
         double T = g.inf;                                 // = lane kl's entry (wave-uniform; see ClGrid::inf)
@@ -781,9 +708,6 @@ __global__ __launch_bounds__(64) void k_cl_core_far(const float4* __restrict__ s
         for (;;) {
             hs = g.inf; T = g.inf;
             auto stream = [&](int j0, int j1) {
-#ifdef VG_DEV
-                if (dbg_scan && u == 0 && lane == 0) { const int w = atomicAdd(&dbg_scan[n + 1], 2); if (w < 200) { dbg_scan[n + 100 + w] = j0; dbg_scan[n + 100 + w + 1] = j1; } }
-#endif
                 for (int base = j0; base < j1; base += 64) {
                     const int j = base + lane;
                     double d2 = INFINITY;
@@ -836,10 +760,6 @@ __global__ __launch_bounds__(64) void k_cl_core_far(const float4* __restrict__ s
             core2[i] = T;
             if (dbg_scan) dbg_scan[i] += scanned;
         }
-#ifdef VG_DEV
-        if (dbg_scan && u == 0 && lane < 16) dbg_scan[n + 16 + lane] = __float_as_int((float)hs);
-        if (dbg_scan && u == 0 && lane == 0) { dbg_scan[n + 2] = i; dbg_scan[n + 3] = L; dbg_scan[n + 4] = __float_as_int((float)T); dbg_scan[n + 5] = __float_as_int((float)bound); }
-#endif
     }
 }
 
@@ -893,7 +813,6 @@ __global__ void k_cl_b_round_init(int n, const int* __restrict__ comp, unsigned 
     if (flags[1]) return;                 // the tree was complete before this round: queued ahead without a host read
     __shared__ unsigned long long blk_max[4];
     int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i == 0) const_cast<int*>(flags)[4] = 0;   // queries the cooperative search hands on to the walk this round
     unsigned long long mine = 0ull;
     if (i < n) {
         best_w[i] = CL_NONE;
@@ -966,7 +885,7 @@ __device__ __forceinline__ unsigned long long cl_edge_key(int oa, int ob) {
 // how many CUs a launch OCCUPIES: a CU that holds any wave of this kernel cannot take a projection-GEMM tile of another frame's ViT pass
 // (that workgroup needs all 160 KB of LDS and every vector register), and the dispatcher deals workgroups round-robin over the CUs:
 // 309 workgroups of 256 threads sit on all 256 CUs for the launch's ~300 us, 155 of 512 threads on 155 (two waves per SIMD either way:
-// 172 registers, 88 KB of stack per CU).  FAR: the far_list / far_flag entry paths of the cooperative search (development build).
+// 172 registers, 88 KB of stack per CU).
 // Measured and dropped (round 5): leaf CHILDREN scanned from their parent's visit.  A walk is a chain of dependent round trips -- one per
 // internal node, two per leaf (its own range, then its points) -- and the parent's trip already brings every child's range and purity, so
 // in near-to-far order the leaf children in front of the first internal child were scanned right there: the same visits in the same order,
@@ -981,7 +900,7 @@ __device__ __forceinline__ unsigned long long cl_edge_key(int oa, int ob) {
 // Measured and dropped (round 4): rounds >= 2 over a compacted list of the points that still have to walk (a few thousand; one 6 us
 // launch builds it): bit-identical, and the rounds take as long as before (332 vs 316 us: a round lasts as long as its longest walks,
 // however few waves carry them) while the pipeline's frames/s do not move (65.1 vs 65.2) -- the walks do not keep GEMM tiles waiting.
-template <int DIM, int NT = 256, bool FAR = false>
+template <int DIM, int NT>
 __global__ __launch_bounds__(NT) void k_cl_b_search(const float4* __restrict__ spts, const float* __restrict__ stt, int n,
                                                      const ClGrid* __restrict__ gp, const int* __restrict__ cs,
                                                      const int* __restrict__ cell_comp, const unsigned int* __restrict__ cell_e,
@@ -993,33 +912,19 @@ __global__ __launch_bounds__(NT) void k_cl_b_search(const float4* __restrict__ s
                                                      unsigned long long* __restrict__ pt_d,
                                                      unsigned long long* __restrict__ pt_key, int* __restrict__ pt_b,
                                                      double* __restrict__ pt_lb, int* __restrict__ dbg_scan, const int* __restrict__ flags,
-                                                     const int* __restrict__ far_list, const int* __restrict__ far_flag,
                                                      const unsigned long long* __restrict__ giant, int sit_min, int xcd_order) {
     if (flags[1]) return;                 // the tree was complete before this round: queued ahead without a host read
     __shared__ unsigned int stack[CL_STACK * NT];
-    // far_list != NULL: only the queries the cooperative search (k_cl_b_search_blk) could not finish inside its shell, each
-    // starting from the best edge it found there (pt_w / pt_d / pt_key / pt_b hold it; pt_b = -1: none)
-    // (far_flag instead of far_list: the same queries, but each in the lane its point index maps to -- 64 hard walks packed into
-    // one wave diverge and run one after the other, spread over all waves they run side by side)
     int a = (xcd_order ? cl_xcd_block(blockIdx.x, gridDim.x) : (int)blockIdx.x) * blockDim.x + threadIdx.x;
-    if (!FAR) { far_list = nullptr; far_flag = nullptr; }
-    if (far_list) {
-        if (a >= flags[4]) return;
-        a = far_list[a];
-    }
     if (a >= n) return;
-    if (far_flag) {
-        if (!far_flag[a]) return;
-        far_list = far_flag;                             // from here on: "start from the edge the point holds"
-    }
     int scanned = 0;
-    if (dbg_scan && !far_list) dbg_scan[a] = 0;
+    if (dbg_scan) dbg_scan[a] = 0;
     unsigned int* st = stack + threadIdx.x;
     const ClGrid g = *gp;
     const float4 qf = spts[a];
     const float qtf = DIM >= 5 ? stt[a] : 0.f;
     const double qx = qf.x, qy = qf.y, qz = qf.z, qe = qf.w, qt = qtf;
-    if (!far_list && pt_b[a] >= 0) return;           // candidate of an earlier round still valid (k_cl_b_seed)
+    if (pt_b[a] >= 0) return;                        // candidate of an earlier round still valid (k_cl_b_seed)
     const int ca = comp[a];
     if (cl_sits_out(*giant, ca, sit_min)) {          // the largest component does not search this round (k_cl_b_round_init)
         pt_w[a] = CL_NONE; pt_d[a] = ~0ull; pt_key[a] = ~0ull; pt_b[a] = -1;
@@ -1052,12 +957,6 @@ __global__ __launch_bounds__(NT) void k_cl_b_search(const float4* __restrict__ s
     unsigned long long bkey = ~0ull;   // ... and its id key -- computed only when an exact (w, d2) tie asks for it, and at the end
     bool bkey_valid = true;
     int bb = -1;
-    if (far_list && pt_b[a] >= 0) {
-        bw = __longlong_as_double((long long)pt_w[a]);
-        bd2 = __longlong_as_double((long long)pt_d[a]);
-        bkey = pt_key[a];
-        bb = pt_b[a];
-    }
     // The slowest WAVE sets the launch time (1 234 waves on 1 024 SIMDs: nothing else hides a wave's stalls), and a wave pays for
     // whatever any of its lanes does (per-thread stamps, round 3: the median wave of round 1 runs 180 us in which its slowest
     // lane waits 6 us for node reads and spends 15-45 us in leaf scans -- the rest is other lanes' scans).  Hence:
@@ -1174,21 +1073,13 @@ __global__ __launch_bounds__(NT) void k_cl_b_search(const float4* __restrict__ s
             const int near = ox | (oy << 1) | (oz << 2);
             double ad[3][2];
             {
-                const double s1 = CL_CELL * (double)(1 << l1);
                 const int nbx[3] = {CL_NX >> l1, CL_NY >> l1, CL_NZ >> l1};
                 const int c2[3] = {2 * x, 2 * y, 2 * z};
                 const double q3[3] = {qx, qy, qz}, o3[3] = {g.ox, g.oy, g.oz};
 #pragma unroll
                 for (int ax = 0; ax < 3; ++ax)
 #pragma unroll
-                    for (int hb = 0; hb < 2; ++hb) {     // the same expressions as cl_box_d2, per axis
-                        const int cc = c2[ax] + hb;
-                        const double lo = o3[ax] + (double)cc * s1, hi = o3[ax] + (double)(cc + 1) * s1;
-                        double d = 0.0;
-                        if (q3[ax] < lo && cc > 0) d = lo - q3[ax];
-                        else if (q3[ax] > hi && cc < nbx[ax] - 1) d = q3[ax] - hi;
-                        ad[ax][hb] = d;
-                    }
+                    for (int hb = 0; hb < 2; ++hb) ad[ax][hb] = cl_axis_gap(o3[ax], q3[ax], c2[ax] + hb, l1, nbx[ax]);
             }
             // child u of the near-first order is octant u ^ near: its range [bnd[u ^ near], bnd[(u ^ near) + 1]) comes out of three conditional
             // exchange stages over the two boundary arrays (48 selects) instead of a 7-deep select chain per child and end (112), and the
@@ -1230,7 +1121,7 @@ __global__ __launch_bounds__(NT) void k_cl_b_search(const float4* __restrict__ s
         }
     }
     if (bb >= 0 && !bkey_valid) bkey = cl_edge_key(oa, perm[bb]);
-    if (dbg_scan) dbg_scan[a] = (far_list ? dbg_scan[a] : 0) + scanned;
+    if (dbg_scan) dbg_scan[a] = scanned;
     if (bb >= 0 && bw <= cbest) {
         pt_w[a] = (unsigned long long)__double_as_longlong(bw);
         pt_d[a] = (unsigned long long)__double_as_longlong(bd2);
@@ -1246,165 +1137,7 @@ __global__ __launch_bounds__(NT) void k_cl_b_search(const float4* __restrict__ s
     }
 }
 
-#ifdef VG_DEV      // measured slower than the walk alone (LAB_NOTES.md section 3, round 3): kept for the A/B tools only, untested in the product
-// Cooperative nearest-foreign search of a Boruvka round (same layout as k_cl_core_blk: one wave per (0.8 m node, 64 queries),
-// lane = query, the 27 neighbour nodes staged in LDS by coalesced loads: coordinates as float64, component id, squared core
-// distance, original id).  A lane keeps the best edge (w, d2, key) it has met under the walk's strict order.  Everything outside
-// the shell is at least r away (r = distance to the shell's outer faces), so its edges weigh >= r^2: a lane whose best edge --
-// or whose component's published bound -- is lighter than that is finished; the others start the tree walk from what they found.
-// A neighbour node is skipped when it is pure and owned by the component of every searching lane, or when it is farther than
-// every searching lane's bounds.
-template <int DIM>
-__global__ __launch_bounds__(64) void k_cl_b_search_blk(const float4* __restrict__ spts, const float* __restrict__ stt, int n,
-                                                        const ClGrid* __restrict__ gp, const int* __restrict__ cs,
-                                                        const unsigned int* __restrict__ code_s, const unsigned int* __restrict__ entries,
-                                                        const int* __restrict__ cell_comp, const int* __restrict__ perm,
-                                                        const double* __restrict__ core2, const int* __restrict__ comp,
-                                                        unsigned long long* __restrict__ best_w, unsigned long long* __restrict__ pt_w,
-                                                        unsigned long long* __restrict__ pt_d, unsigned long long* __restrict__ pt_key,
-                                                        int* __restrict__ pt_b, double* __restrict__ pt_lb, int* __restrict__ dbg_scan,
-                                                        int* __restrict__ flags, int* __restrict__ far_list, int* __restrict__ far_flag) {
-    if (flags[1]) return;
-    __shared__ int bnd[27][3];                        // range + purity of the 27 neighbour nodes
-    __shared__ ClbPlan plan;
-    __shared__ double tile[DIM + 1][CLB_TILE];        // coordinates, squared core distance
-    __shared__ int tile_i[2][CLB_TILE];               // component, original id
-    const int lane = threadIdx.x;
-    const ClGrid g = *gp;
-    const int n_entries = flags[2];
-    for (int e = blockIdx.x; e < n_entries; e += gridDim.x) {
-        const int lv = (int)(entries[e] >> 30), i0 = (int)(entries[e] & 0x3FFFFFFFu);   // node level (0 .. 3), first query
-        const unsigned int key1 = code_s[i0] >> (3 * lv);
-        const int iend = min(cl_start_l(cs, lv, key1 + 1u), i0 + 64);
-        const int a = i0 + lane;
-        const bool active = a < iend;
-        const int aa = active ? a : i0;
-        bool searching = active && pt_b[aa] < 0;      // a candidate of an earlier round that is still foreign is kept (k_cl_b_seed)
-        if (far_flag && active) far_flag[a] = 0;
-        if (!__any(searching)) continue;
-        const float4 qf = spts[aa];
-        const double qx = qf.x, qy = qf.y, qz = qf.z, qe = qf.w, qt = DIM >= 5 ? (double)stt[aa] : 0.0;
-        const int ca = comp[aa];
-        const double core_a = core2[aa];
-        const double lb_a = fmax(core_a, pt_lb[aa]);
-        double cbest = g.inf;
-        {
-            const unsigned long long cb0 = __hip_atomic_load(&best_w[ca], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (cb0 != CL_NONE) cbest = __longlong_as_double((long long)cb0);
-        }
-        if (searching && lb_a > cbest) {              // cannot supply its component's edge (same exit as the walk)
-            pt_w[a] = CL_NONE; pt_d[a] = ~0ull; pt_key[a] = ~0ull; pt_b[a] = -1;
-            searching = false;
-        }
-        if (!__any(searching)) continue;
-        const int oa = perm[aa];
-        int bx, by, bz;
-        {
-            const float4 f0 = spts[i0];
-            cl_cell_of(g, (double)f0.x, (double)f0.y, (double)f0.z, bx, by, bz);
-            bx >>= lv; by >>= lv; bz >>= lv;
-        }
-        __syncthreads();
-        if (lane < 27) {
-            const int nx = bx + CLB_ORDER[lane][0], ny = by + CLB_ORDER[lane][1], nz = bz + CLB_ORDER[lane][2];
-            int j0 = 0, j1 = 0, pure = -1;
-            if (nx >= 0 && ny >= 0 && nz >= 0 && nx < (CL_NX >> lv) && ny < (CL_NY >> lv) && nz < (CL_NZ >> lv)) {
-                const unsigned int c0 = cl_code(nx << lv, ny << lv, nz << lv);
-                j0 = cl_start_l(cs, lv, c0 >> (3 * lv));
-                j1 = cl_start_l(cs, lv, (c0 >> (3 * lv)) + 1u);
-                if (j0 != j1) pure = cell_comp[cl_pur_off(lv) + (c0 >> (3 * lv))];
-            }
-            bnd[lane][0] = j0; bnd[lane][1] = j1; bnd[lane][2] = pure;
-        }
-        __syncthreads();
-        double bw = g.inf, bd2 = g.inf;
-        unsigned long long bkey = ~0ull;
-        int bb = -1, scanned = 0;
-        int t_next = 0, cur = bnd[0][0];
-        while (t_next < 27) {
-            int nseg = 0, tot = 0;
-            while (t_next < 27 && tot < CLB_TILE) {
-                const int j1 = bnd[t_next][1], pure = bnd[t_next][2];
-                bool need = cur < j1;
-                if (need) {
-                    const double nd2 = cl_box_d2(g, qx, qy, qz, lv, bx + CLB_ORDER[t_next][0], by + CLB_ORDER[t_next][1], bz + CLB_ORDER[t_next][2]);
-                    const double lb = fmax(lb_a, nd2);
-                    need = __any(searching && pure != ca && !(lb > bw || lb > cbest || (lb == bw && nd2 > bd2)));
-                }
-                if (need) {
-                    const int take = min(j1 - cur, CLB_TILE - tot);
-                    if (lane == 0) { plan.start[nseg] = cur; plan.take[nseg] = take; plan.off[nseg] = tot; }
-                    ++nseg; tot += take; cur += take;
-                    if (cur < j1) break;
-                }
-                ++t_next;
-                if (t_next < 27) cur = bnd[t_next][0];
-            }
-            if (tot == 0) break;
-            __syncthreads();
-#pragma unroll
-            for (int r = 0; r < CLB_TILE / 64; ++r) {
-                const int f = lane + 64 * r;
-                if (f < tot) {
-                    const int j = clb_locate(plan, nseg, f);
-                    const float4 p = spts[j];
-                    tile[0][f] = (double)p.x; tile[1][f] = (double)p.y; tile[2][f] = (double)p.z;
-                    if (DIM >= 4) tile[3 < DIM ? 3 : 0][f] = (double)p.w;
-                    if (DIM >= 5) tile[4 < DIM ? 4 : 0][f] = (double)stt[j];
-                    tile[DIM][f] = core2[j];
-                    tile_i[0][f] = comp[j];
-                    tile_i[1][f] = j;
-                }
-            }
-            __syncthreads();
-            scanned += tot;
-            for (int c = 0; c < tot; ++c) {
-                if (tile_i[0][c] == ca) continue;
-                const double dx = qx - tile[0][c], dy = qy - tile[1][c], dz = qz - tile[2][c];
-                double d2 = (dx * dx + dy * dy) + dz * dz;
-                if (DIM >= 4) { const double de = qe - tile[3 < DIM ? 3 : 0][c]; d2 = d2 + de * de; }
-                if (DIM >= 5) { const double dt = qt - tile[4 < DIM ? 4 : 0][c]; d2 = d2 + dt * dt; }
-                if (d2 > bw) continue;
-                const double w = fmax(fmax(d2, core_a), tile[DIM][c]);
-                if (w > bw || (w == bw && d2 > bd2)) continue;
-                const int j = tile_i[1][c];
-                const unsigned long long key = cl_edge_key(oa, perm[j]);   // (rare: only for edges that tie or win)
-                if (w < bw || d2 < bd2 || key < bkey) { bw = w; bd2 = d2; bkey = key; bb = j; }
-            }
-        }
-        if (searching) {
-            if (bb >= 0) atomicMin(&best_w[ca], (unsigned long long)__double_as_longlong(bw));
-            const unsigned long long cb = __hip_atomic_load(&best_w[ca], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            cbest = cb == CL_NONE ? g.inf : __longlong_as_double((long long)cb);
-        }
-        const double r2 = cl_block_radius2(g, qx, qy, qz, bx, by, bz, lv);
-        const bool done = fmin(bw, cbest) < r2;           // strictly lighter than anything outside the shell
-        if (searching) {
-            if (dbg_scan) dbg_scan[a] = scanned;
-            if (done && !(bb >= 0 && bw <= cbest)) {
-                if (cbest < g.inf && cbest > pt_lb[a]) pt_lb[a] = cbest;
-                pt_w[a] = CL_NONE; pt_d[a] = ~0ull; pt_key[a] = ~0ull; pt_b[a] = -1;
-            } else {                                      // final (done), or the walk's starting point
-                pt_w[a] = bb >= 0 ? (unsigned long long)__double_as_longlong(bw) : CL_NONE;
-                pt_d[a] = bb >= 0 ? (unsigned long long)__double_as_longlong(bd2) : ~0ull;
-                pt_key[a] = bkey;
-                pt_b[a] = bb;
-                if (done) pt_lb[a] = bw;
-            }
-        }
-        const unsigned long long far = __ballot(searching && !done);
-        if (far) {
-            int base = 0;
-            if (lane == 0) base = atomicAdd(&flags[4], __popcll(far));
-            base = __shfl(base, 0);
-            if (searching && !done) far_list[base + __popcll(far & ((1ull << lane) - 1ull))] = a;
-            if (far_flag && searching && !done) far_flag[a] = 1;
-        }
-    }
-}
-
 // per component: smallest w (atomicMin in the search), then smallest d2 among those, then smallest id key among those
-#endif  // VG_DEV
 __global__ void k_cl_b_select_d(int n, const int* __restrict__ comp, const unsigned long long* __restrict__ best_w,
                                 const unsigned long long* __restrict__ pt_w, const unsigned long long* __restrict__ pt_d,
                                 unsigned long long* __restrict__ best_d, const int* __restrict__ flags) {
@@ -1490,20 +1223,6 @@ __global__ void k_cl_b_compress(int n, int* __restrict__ comp, const int* __rest
     aux[i].z = r;
 }
 
-#ifdef VG_DEV
-// Experiment (round 5, VG_CLUSTER_SEEDSIM=1): what would round 1 of the Boruvka search cost if every point whose best edge weighs exactly its
-// own core distance -- the points a pass over the k-NN shell could seed without a walk -- were answered beforehand?  After round 1's search
-// the candidates of all OTHER points are dropped and the search is launched again: that second launch walks only the points a seed could
-// not serve (same results; its duration in the kernel trace is the residual walk).
-__global__ void k_cl_seedsim_drop(int n, const double* __restrict__ core2, const unsigned long long* __restrict__ pt_w, int* __restrict__ pt_b,
-                                  int* __restrict__ counter) {
-    const int a = blockIdx.x * blockDim.x + threadIdx.x;
-    if (a >= n) return;
-    const bool seedable = pt_b[a] >= 0 && pt_w[a] == (unsigned long long)__double_as_longlong(core2[a]);
-    if (!seedable) { pt_b[a] = -1; atomicAdd(&counter[5], 1); }
-}
-#endif
-
 __global__ void k_cl_iota(int n, int* p) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) p[i] = i;
@@ -1544,7 +1263,7 @@ __device__ __forceinline__ float cl_cell_d2_lb(const ClGrid& g, float qx, float 
     float d2 = 0.f;
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
-        const float lo = (float)(o[a] + (double)c[a] * CL_CELL), hi = (float)(o[a] + (double)(c[a] + 1) * CL_CELL);
+        const float lo = (float)cl_face(o[a], c[a], 0), hi = (float)cl_face(o[a], c[a] + 1, 0);
         float d = 0.f;
         if (q[a] < lo && c[a] > 0) d = lo - q[a];
         else if (q[a] > hi && c[a] < nb[a] - 1) d = q[a] - hi;
@@ -1618,14 +1337,9 @@ struct MinOp {
     __device__ __host__ int operator()(int a, int b) const { return a < b ? a : b; }
 };
 
-extern "C" {
-
-int vg_cluster_create(vg_cluster** out, int max_points) {
-    if (!out || max_points <= 0) return VG_ERR_ARG;
-    vg_cluster* h = new vg_cluster();
-    memset(h, 0, sizeof(*h));
-    h->max_points = max_points;
-    const size_t n = (size_t)max_points;
+// every buffer of a handle whose members are all null (vg_cluster_create frees what is there when this fails half-way)
+static int cl_alloc(vg_cluster* h) {
+    const size_t n = (size_t)h->max_points;
     VG_CHECK(hipMalloc(&h->d_grid, sizeof(ClGrid)));
     VG_CHECK(hipMalloc(&h->d_code, 4 * n));
     VG_CHECK(hipMalloc(&h->d_code_s, 4 * n));
@@ -1643,7 +1357,6 @@ int vg_cluster_create(vg_cluster** out, int max_points) {
     VG_CHECK(hipMalloc(&h->d_core2, 8 * n));
     VG_CHECK(hipMalloc(&h->d_comp, 4 * n));
     VG_CHECK(hipMalloc(&h->d_aux, 16 * n));
-    VG_CHECK(hipMalloc(&h->d_parent, 4 * n));
     VG_CHECK(hipMalloc(&h->d_parent2, 4 * n));
     VG_CHECK(hipMalloc(&h->d_best_w, 8 * n));
     VG_CHECK(hipMalloc(&h->d_best_e, 8 * n));
@@ -1660,8 +1373,6 @@ int vg_cluster_create(vg_cluster** out, int max_points) {
     VG_CHECK(hipMalloc(&h->d_giant, 8));
     VG_CHECK(hipMalloc(&h->d_entries, 4 * n));
     VG_CHECK(hipMalloc(&h->d_far, 4 * n));
-    VG_CHECK(hipMalloc(&h->d_far_flag, 4 * n));
-    VG_CHECK(hipMemset(h->d_far_flag, 0, 4 * n));
     VG_CHECK(hipMalloc(&h->d_mst_a, 4 * n));
     VG_CHECK(hipMalloc(&h->d_mst_b, 4 * n));
     VG_CHECK(hipMalloc(&h->d_mst_w, 8 * n));
@@ -1669,7 +1380,6 @@ int vg_cluster_create(vg_cluster** out, int max_points) {
     VG_CHECK(hipMalloc(&h->d_mst_idx, 4 * n));
     VG_CHECK(hipMalloc(&h->d_mst_idx_s, 4 * n));
     VG_CHECK(hipHostMalloc((void**)&h->h_counter, 64));
-    h->d_dbg = nullptr;
     if (getenv("VG_CLUSTER_DEBUG")) VG_CHECK(hipMalloc(&h->d_dbg, 4 * n));
     size_t t1 = 0, t2 = 0, t3 = 0;
     VG_CHECK(rocprim::radix_sort_pairs(nullptr, t1, h->d_code, h->d_code_s, h->d_perm_in, h->d_perm, n, 0, 24));
@@ -1677,6 +1387,21 @@ int vg_cluster_create(vg_cluster** out, int max_points) {
     VG_CHECK(rocprim::inclusive_scan(nullptr, t3, h->d_cell_start, h->d_cell_start, (size_t)(CL_NCODES + 1), MinOp()));
     h->temp_bytes = std::max(t1, std::max(t2, t3)) + 256;
     VG_CHECK(hipMalloc(&h->d_temp, h->temp_bytes));
+    return VG_OK;
+}
+
+extern "C" {
+
+int vg_cluster_create(vg_cluster** out, int max_points) {
+    if (!out || max_points <= 0) return VG_ERR_ARG;
+    vg_cluster* h = new vg_cluster();
+    memset(h, 0, sizeof(*h));
+    h->max_points = max_points;
+    const int rc = cl_alloc(h);
+    if (rc != VG_OK) {
+        vg_cluster_destroy(h);
+        return rc;
+    }
     *out = h;
     return VG_OK;
 }
@@ -1684,9 +1409,9 @@ int vg_cluster_create(vg_cluster** out, int max_points) {
 void vg_cluster_destroy(vg_cluster* h) {
     if (!h) return;
     void* ptrs[] = {h->d_grid, h->d_code, h->d_code_s, h->d_perm_in, h->d_perm, h->d_spts, h->d_st, h->d_cell_start, h->d_cell_comp, h->d_cell_e,
-                    h->d_core2, h->d_comp, h->d_parent, h->d_parent2, h->d_best_w, h->d_best_e, h->d_sel_a, h->d_sel_b,
+                    h->d_core2, h->d_comp, h->d_parent2, h->d_best_w, h->d_best_e, h->d_sel_a, h->d_sel_b,
                     h->d_pt_w, h->d_pt_key, h->d_pt_d, h->d_pt_lb, h->d_best_d, h->d_pt_b, h->d_counter, h->d_mst_a, h->d_mst_b, h->d_mst_w, h->d_mst_w_s,
-                    h->d_mst_idx, h->d_mst_idx_s, h->d_temp, h->d_entries, h->d_far, h->d_far_flag, h->d_aux, h->d_csize, h->d_giant};
+                    h->d_mst_idx, h->d_mst_idx_s, h->d_temp, h->d_entries, h->d_far, h->d_aux, h->d_csize, h->d_giant, h->d_dbg};
     for (void* p : ptrs) (void)hipFree(p);
     (void)hipHostFree(h->h_counter);
     delete h;
@@ -1721,108 +1446,85 @@ static int cl_build_grid(vg_cluster* h, const float* d_points, int n, int stride
     return VG_OK;
 }
 
+// VG_CLUSTER_DEBUG=1: the per-query counts of d_dbg once the stream has drained, sorted, with their total and how many are not zero
+struct ClDbgCounts {
+    std::vector<int> sorted;
+    long long total = 0;
+    int nonzero = 0;
+    int at(int num, int den) const { return sorted[sorted.size() * (size_t)num / (size_t)den]; }      // the num / den quantile
+    int max() const { return sorted.back(); }
+};
+static ClDbgCounts cl_dbg_counts(vg_cluster* h, int n, hipStream_t st) {
+    ClDbgCounts c;
+    c.sorted.resize(n);
+    (void)hipStreamSynchronize(st);
+    (void)hipMemcpy(c.sorted.data(), h->d_dbg, 4 * (size_t)n, hipMemcpyDeviceToHost);
+    for (int v : c.sorted) { c.total += v; c.nonzero += v > 0; }
+    std::sort(c.sorted.begin(), c.sorted.end());
+    return c;
+}
+
+// body(std::integral_constant<int, dim>): the ONE place that turns the run-time dim (3, 4 or 5) into the kernels' template parameter
+template <typename Body>
+static int cl_with_dim(int dim, Body&& body) {
+    if (dim == 3) return body(std::integral_constant<int, 3>());
+    if (dim == 4) return body(std::integral_constant<int, 4>());
+    return body(std::integral_constant<int, 5>());
+}
+
+// What an MST reads ONCE and hands to every launch of every round.  The product's values are fixed; the development build reads its
+// switches into them, once per MST too -- a switch that a tool flips between a round's search and pick launches would let pick accept
+// candidates of a component that did not search.
+struct ClSwitches {
+    int sit_min;          // smallest size at which the largest component sits a round out (k_cl_b_round_init): an eighth of the points
+    int xcd_order;        // the walk's workgroups in cl_xcd_block order
+    int first_batch;      // Boruvka rounds queued before the first host read of the edge counter
+};
+
+// the walk of one Boruvka round: THE launch of k_cl_b_search (the product's NT is 512: see the kernel)
+template <int DIM, int NT>
+static void cl_launch_walk(vg_cluster* h, int n, hipStream_t st, int sit_min, int xcd_order) {
+    hipLaunchKernelGGL((k_cl_b_search<DIM, NT>), dim3(vg_div_up(n, NT)), dim3(NT), 0, st, h->d_spts, h->d_st, n, h->d_grid, h->d_cell_start,
+                       h->d_cell_comp, h->d_cell_e, h->d_perm, h->d_core2, h->d_comp, h->d_aux, h->d_best_w, h->d_pt_w, h->d_pt_d, h->d_pt_key,
+                       h->d_pt_b, h->d_pt_lb, h->d_dbg, h->d_counter, h->d_giant, sit_min, xcd_order);
+}
+
+#ifdef VG_DEV      // the development build's kernels, switches and simulations: cl_dev_switches, cl_dev_core_walk, cl_dev_round_search
+#include "dev/cluster_dev.inc"
+#endif
+
 // the two cooperative phases in one form (List / WIDE: see k_cl_core_blk)
 template <int DIM, typename List, bool WIDE>
-static void cl_launch_core_phases(vg_cluster* h, int n, int k, hipStream_t st, bool no_far, int far_level) {
+static void cl_launch_core_phases(vg_cluster* h, int n, int k, hipStream_t st) {
     hipLaunchKernelGGL((k_cl_core_blk<DIM, List>), dim3(std::min(n, 16384)), dim3(64), 0, st, h->d_spts, h->d_st, n, h->d_grid, h->d_cell_start,
                        h->d_code_s, h->d_entries, h->d_counter, k, h->d_core2, h->d_far, h->d_dbg);
-    if (!no_far)
-        hipLaunchKernelGGL((k_cl_core_far<DIM, WIDE>), dim3(std::min(n, 8192)), dim3(64), 0, st, h->d_spts, h->d_st, n, h->d_grid, h->d_cell_start,
-                           h->d_far, h->d_counter, k, h->d_core2, h->d_dbg, far_level);
+    hipLaunchKernelGGL((k_cl_core_far<DIM, WIDE>), dim3(std::min(n, 8192)), dim3(64), 0, st, h->d_spts, h->d_st, n, h->d_grid, h->d_cell_start,
+                       h->d_far, h->d_counter, k, h->d_core2, h->d_dbg);
 }
 
 template <int DIM>
 static void cl_launch_core(vg_cluster* h, int n, int k, hipStream_t st) {
+    bool walked = false;                              // (the per-point walk ran instead: no work list, no far phase)
 #ifdef VG_DEV
-    static const int walk = getenv("VG_CLUSTER_CORE_WALK") ? atoi(getenv("VG_CLUSTER_CORE_WALK")) : 0;   // 1: the per-point tree walk (A/B aid, development build)
-    const bool no_far = getenv("VG_CLUSTER_CORE_NOFAR") != nullptr;
-    const int far_level = getenv("VG_CLUSTER_FAR_LEVEL") ? atoi(getenv("VG_CLUSTER_FAR_LEVEL")) : 0;
-#else
-    constexpr int walk = 0, far_level = 0;
-    constexpr bool no_far = false;
+    walked = cl_dev_core_walk<DIM>(h, n, k, st);
 #endif
-#ifdef VG_DEV
-    if (walk && k < CL_K) {
-        hipLaunchKernelGGL((k_cl_core<DIM>), dim3(vg_div_up(n, 256)), dim3(256), 0, st, h->d_spts, h->d_st, n, h->d_grid,
-                           h->d_cell_start, h->d_cell_e, k, h->d_core2, h->d_dbg);
-    } else
-#endif
-    {
-        // counters[2] = work-list entries of phase A (kept for the Boruvka rounds), counters[3] = queries left for phase B
+    if (!walked) {
+        // counters[2] = work-list entries of phase A, counters[3] = queries left for phase B
         (void)hipMemsetAsync(h->d_counter + 2, 0, 8, st);
         hipLaunchKernelGGL(k_cl_blocks, dim3(vg_div_up(n, 256)), dim3(256), 0, st, n, h->d_code_s, h->d_cell_start, h->d_entries, h->d_counter);
-        if (k < CL_K) cl_launch_core_phases<DIM, ClRegList, false>(h, n, k, st, no_far, far_level);
-        else if (k <= 32) cl_launch_core_phases<DIM, ClLdsHeap<32>, true>(h, n, k, st, no_far, far_level);
-        else cl_launch_core_phases<DIM, ClLdsHeap<64>, true>(h, n, k, st, no_far, far_level);
+        if (k < CL_K) cl_launch_core_phases<DIM, ClRegList, false>(h, n, k, st);
+        else if (k <= 32) cl_launch_core_phases<DIM, ClLdsHeap<32>, true>(h, n, k, st);
+        else cl_launch_core_phases<DIM, ClLdsHeap<64>, true>(h, n, k, st);
     }
     if (h->d_dbg) {
         // VG_CLUSTER_DEBUG=1: pairs evaluated / pairs needed: the exact answer needs n * k distances
-        std::vector<int> sc(n);
+        const ClDbgCounts sc = cl_dbg_counts(h, n, st);
         int cnt[4] = {0, 0, 0, 0};
-        (void)hipStreamSynchronize(st);
-        (void)hipMemcpy(sc.data(), h->d_dbg, 4 * (size_t)n, hipMemcpyDeviceToHost);
         (void)hipMemcpy(cnt, h->d_counter, 16, hipMemcpyDeviceToHost);
-        long long tot = 0;
-        for (int v : sc) tot += v;
-        std::sort(sc.begin(), sc.end());
         fprintf(stderr, "[cluster dbg] core distances: n %d, k %d, pair distances evaluated %lld = %.1f x the %lld needed (n*k); per point median %d, p99 %d, max %d"
                         "; cooperative: %d (node, 64-query) work items, %d queries left to the far phase\n",
-                n, k, tot, (double)tot / ((double)n * k), (long long)n * k, sc[n / 2], sc[(size_t)n * 99 / 100], sc[n - 1], walk ? 0 : cnt[2], walk ? 0 : cnt[3]);
+                n, k, sc.total, (double)sc.total / ((double)n * k), (long long)n * k, sc.at(1, 2), sc.at(99, 100), sc.max(), walked ? 0 : cnt[2], walked ? 0 : cnt[3]);
     }
-}
-// smallest size at which the largest component sits a round out (k_cl_b_round_init): an eighth of the points
-static int cl_sit_min(int n) {
-#ifdef VG_DEV
-    const char* e = getenv("VG_CLUSTER_SITOUT");           // A/B aid (development build), read per call: tools switch it inside one process
-    if (e && atoi(e) == 0) return 0x7FFFFFFF;
-#endif
-    return std::max(2, n / 8);
-}
-// (sit_min, xcd_order: read ONCE per MST by the caller and handed to every launch of every round -- a development switch that a tool flips
-// between a round's search and pick launches would let pick accept candidates of a component that did not search)
-template <int DIM>
-static void cl_launch_search(vg_cluster* h, int n, hipStream_t st, int sit_min, int xcd_order) {
-#ifdef VG_DEV
-    // VG_CLUSTER_SEARCH_NT (A/B aid, development build): threads per workgroup of the walk, 256, 512 or 768 (see k_cl_b_search)
-    const char* nt_env = getenv("VG_CLUSTER_SEARCH_NT");          // (read per launch: the A/B tool switches it inside one process)
-    const int nt = nt_env ? atoi(nt_env) : 512;
-#else
-    constexpr int nt = 512;
-#endif
-#ifdef VG_DEV
-    // VG_CLUSTER_SEARCH_MODE (A/B aid, development build): 0 = the tree walk alone, 1 = cooperative search, leftovers walk as a compacted
-    // list, 2 = cooperative search, leftovers walk in place.  Measured on 150k-point frames the cooperative search + the leftover walks
-    // take longer than the walk alone (LAB_NOTES.md section 3)
-    static const int mode = getenv("VG_CLUSTER_SEARCH_MODE") ? atoi(getenv("VG_CLUSTER_SEARCH_MODE")) : 0;
-    static const int core_walk = getenv("VG_CLUSTER_CORE_WALK") ? atoi(getenv("VG_CLUSTER_CORE_WALK")) : 0;  // (no work list then)
-    if (mode != 0 && !core_walk) {
-        hipLaunchKernelGGL((k_cl_b_search_blk<DIM>), dim3(std::min(n, 16384)), dim3(64), 0, st, h->d_spts, h->d_st, n, h->d_grid, h->d_cell_start,
-                           h->d_code_s, h->d_entries, h->d_cell_comp, h->d_perm, h->d_core2, h->d_comp, h->d_best_w, h->d_pt_w, h->d_pt_d, h->d_pt_key,
-                           h->d_pt_b, h->d_pt_lb, h->d_dbg, h->d_counter, h->d_far, mode == 2 ? h->d_far_flag : (int*)nullptr);
-        // the queries left over walk the tree from the edge they hold
-        hipLaunchKernelGGL((k_cl_b_search<DIM, 256, true>), dim3(vg_div_up(n, 256)), dim3(256), 0, st, h->d_spts, h->d_st, n, h->d_grid,
-                           h->d_cell_start, h->d_cell_comp, h->d_cell_e, h->d_perm, h->d_core2, h->d_comp, h->d_aux, h->d_best_w, h->d_pt_w, h->d_pt_d,
-                           h->d_pt_key, h->d_pt_b, h->d_pt_lb, h->d_dbg, h->d_counter, mode == 1 ? (const int*)h->d_far : (const int*)nullptr,
-                           mode == 2 ? (const int*)h->d_far_flag : (const int*)nullptr, h->d_giant, sit_min, 0);
-        return;
-    }
-#endif
-#ifdef VG_DEV
-    if (nt == 768) {      // three waves per SIMD (<= 168 registers, 132 KB of stack): 103 instead of 155 workgroups for 79k points (A/B, round 6)
-        hipLaunchKernelGGL((k_cl_b_search<DIM, 768>), dim3(vg_div_up(n, 768)), dim3(768), 0, st, h->d_spts, h->d_st, n, h->d_grid,
-                           h->d_cell_start, h->d_cell_comp, h->d_cell_e, h->d_perm, h->d_core2, h->d_comp, h->d_aux, h->d_best_w, h->d_pt_w, h->d_pt_d,
-                           h->d_pt_key, h->d_pt_b, h->d_pt_lb, h->d_dbg, h->d_counter, (const int*)nullptr, (const int*)nullptr, h->d_giant, sit_min, xcd_order);
-        return;
-    }
-#endif
-    if (nt == 512)
-        hipLaunchKernelGGL((k_cl_b_search<DIM, 512>), dim3(vg_div_up(n, 512)), dim3(512), 0, st, h->d_spts, h->d_st, n, h->d_grid,
-                           h->d_cell_start, h->d_cell_comp, h->d_cell_e, h->d_perm, h->d_core2, h->d_comp, h->d_aux, h->d_best_w, h->d_pt_w, h->d_pt_d,
-                           h->d_pt_key, h->d_pt_b, h->d_pt_lb, h->d_dbg, h->d_counter, (const int*)nullptr, (const int*)nullptr, h->d_giant, sit_min, xcd_order);
-    else
-        hipLaunchKernelGGL((k_cl_b_search<DIM, 256>), dim3(vg_div_up(n, 256)), dim3(256), 0, st, h->d_spts, h->d_st, n, h->d_grid,
-                           h->d_cell_start, h->d_cell_comp, h->d_cell_e, h->d_perm, h->d_core2, h->d_comp, h->d_aux, h->d_best_w, h->d_pt_w, h->d_pt_d,
-                           h->d_pt_key, h->d_pt_b, h->d_pt_lb, h->d_dbg, h->d_counter, (const int*)nullptr, (const int*)nullptr, h->d_giant, sit_min, xcd_order);
 }
 
 extern "C" {
@@ -1918,113 +1620,59 @@ int vg_cluster_geom_probe(const double* h_origin_in, const float* h_bbox_lo, con
     return VG_OK;
 }
 
-/* Exact core distances + exact MST of the mutual reachability graph.  SYNCHRONOUS on `stream` (one small
- * device->host counter read per Boruvka round).
- *   d_points [n,stride] f32; dim = 3, 4 or 5 leading columns form the clustering space (x,y,z first: the cell grid and
- *   all pruning bounds use x,y,z only -- a lower bound of the dim-D distance; 5-D = the two-frame input of
- *   zero_shot_detector.py:232-237: x,y,z,entropy,0.1*frame).  Distances: float64, summed left to right.
- *   k = min_samples (1 .. VG_CLUSTER_MAX_K): core = distance to the k-th nearest OTHER point (k <= 15: register lists,
- *   k >= 16: ClLdsHeap / the WIDE form of k_cl_core_far)
- *   d_core2  [n] f64 squared core distances, ORIGINAL point order (may be NULL)
- *   d_mst_lo/hi [n-1] int32 original point ids (lo < hi), d_mst_w2 [n-1] f64 squared weights, sorted ascending by
- *   weight (equal weights in unspecified order: vg_hdbscan_tree_host callers sort ties by (lo,hi)).
- *   h_rounds: number of Boruvka rounds (diagnostic, may be NULL). */
-int vg_cluster_mst_nd(vg_cluster* h, const float* d_points, int n, int stride, int dim, int k, double* d_core2,
-                      int32_t* d_mst_lo, int32_t* d_mst_hi, double* d_mst_w2, int32_t* h_rounds, void* stream) {
-    if (!h || !d_points || n < 0 || dim < 3 || dim > 5 || stride < dim || k < 1 || k > VG_CLUSTER_MAX_K) return VG_ERR_ARG;
-    if (n > h->max_points) return VG_ERR_CAPACITY;
-    if (h_rounds) *h_rounds = 0;
-    if (n < 2) return VG_OK;
-    hipStream_t st = (hipStream_t)stream;
+}  // extern "C"
+
+// vg_cluster_mst_nd behind its argument checks, for one clustering space
+template <int DIM>
+static int cl_mst(vg_cluster* h, const float* d_points, int n, int stride, int k, double* d_core2, int32_t* d_mst_lo, int32_t* d_mst_hi,
+                  double* d_mst_w2, int32_t* h_rounds, hipStream_t st) {
     const int nb = vg_div_up(n, 256);
     {
-        const int rc = cl_build_grid(h, d_points, n, stride, dim, st);
+        const int rc = cl_build_grid(h, d_points, n, stride, DIM, st);
         if (rc != VG_OK) return rc;
     }
-    if (dim >= 4) {
+    if (DIM >= 4) {
         hipLaunchKernelGGL(k_cl_e_leaf, dim3(nb), dim3(256), 0, st, n, h->d_code_s, h->d_spts, h->d_cell_e);
         for (int l = 1; l < CL_PUR_LEVELS; ++l)
             hipLaunchKernelGGL(k_cl_e_up, dim3(nb), dim3(256), 0, st, n, l, h->d_code_s, h->d_cell_start, h->d_cell_e);
     }
-    if (dim == 3) cl_launch_core<3>(h, n, k, st);
-    else if (dim == 4) cl_launch_core<4>(h, n, k, st);
-    else cl_launch_core<5>(h, n, k, st);
+    cl_launch_core<DIM>(h, n, k, st);
     if (d_core2) hipLaunchKernelGGL(k_cl_unsort_core, dim3(nb), dim3(256), 0, st, n, h->d_perm, h->d_core2, d_core2);
     VG_LAUNCH_CHECK();
     // ---- Boruvka ----
     hipLaunchKernelGGL(k_cl_b_init, dim3(nb), dim3(256), 0, st, n, h->d_comp, h->d_counter, h->d_pt_b, h->d_pt_lb, h->d_core2,
-                       dim >= 5 ? h->d_st : (const float*)nullptr, h->d_aux, h->d_csize, h->d_giant);
+                       DIM >= 5 ? h->d_st : (const float*)nullptr, h->d_aux, h->d_csize, h->d_giant);
     // Rounds are queued in batches WITHOUT a host read in between: every round's kernels start with `if (flags[1]) return`,
     // and k_cl_b_compress sets flags[1] once the n - 1 edges are out, so a round queued after the last needed one costs a
     // dozen empty launches.  The edge count of every round is copied to its own pinned slot; the host reads them once per batch
     // (first batch: CL_FIRST_BATCH rounds -- 150k-point frames need 6-8 -- then one round at a time).
     int rounds = 0, edges = 0, needed = 0;
     int* const flags = h->d_counter;
-    int first_batch = CL_FIRST_BATCH;
+    ClSwitches sw = {std::max(2, n / 8), 1, CL_FIRST_BATCH};      // one reading per MST
 #ifdef VG_DEV
-    if (getenv("VG_CLUSTER_FIRST_BATCH")) first_batch = std::max(1, std::min(12, atoi(getenv("VG_CLUSTER_FIRST_BATCH"))));
-#endif
-    const int sit_min = cl_sit_min(n);             // development switches: one reading per MST
-    int xcd_order = 1;
-#ifdef VG_DEV
-    if (getenv("VG_CLUSTER_XCD_ORDER")) xcd_order = atoi(getenv("VG_CLUSTER_XCD_ORDER"));
+    cl_dev_switches(&sw);
 #endif
     auto one_round = [&](int r) {
         hipLaunchKernelGGL(k_cl_b_round_init, dim3(nb), dim3(256), 0, st, n, h->d_comp, h->d_best_w, h->d_best_d, h->d_best_e, h->d_sel_a, flags, h->d_csize, h->d_giant, h->d_code_s, h->d_cell_comp);
         if (r > 1) hipLaunchKernelGGL(k_cl_b_seed, dim3(nb), dim3(256), 0, st, n, h->d_comp, h->d_pt_b, h->d_pt_w, h->d_best_w, flags);
         hipLaunchKernelGGL(k_cl_b_purity, dim3(nb), dim3(256), 0, st, n, h->d_code_s, h->d_comp, h->d_cell_comp, flags);
-#ifdef VG_DEV
-        // VG_CLUSTER_BOUNDSIM (round 6, VERDICT r5 task 6: would a component-level search pay?).  What a workgroup-per-component search adds
-        // to this walk is a component bound every point sees AT ONCE (here: published through best_w by atomicMin, read at the start and every
-        // 8th node).  Simulated before being built: every round's search is launched a SECOND time with best_w already holding each
-        // component's final minimum (candidates and lower bounds restored to their state in front of the first launch) -- no shared bound
-        // can prune more than the true one from the first node on.  The second launches' durations are the floor of that family.
-        static const bool boundsim = getenv("VG_CLUSTER_BOUNDSIM") != nullptr;
-        static int* sim_b = nullptr; static double* sim_lb = nullptr; static int sim_n = 0;
-        if (boundsim) {
-            if (sim_n < n) { (void)hipFree(sim_b); (void)hipFree(sim_lb); (void)hipMalloc(&sim_b, (size_t)n * 4); (void)hipMalloc(&sim_lb, (size_t)n * 8); sim_n = n; }
-            (void)hipMemcpyAsync(sim_b, h->d_pt_b, (size_t)n * 4, hipMemcpyDeviceToDevice, st);
-            (void)hipMemcpyAsync(sim_lb, h->d_pt_lb, (size_t)n * 8, hipMemcpyDeviceToDevice, st);
-            if (dim == 3) cl_launch_search<3>(h, n, st, sit_min, xcd_order);
-            else if (dim == 4) cl_launch_search<4>(h, n, st, sit_min, xcd_order);
-            else cl_launch_search<5>(h, n, st, sit_min, xcd_order);
-            // best_w now holds every component's minimum: search again from the same candidates / lower bounds (this launch's outputs are the
-            // ones the round goes on with: the same edges -- tests still pass with the switch on)
-            (void)hipMemcpyAsync(h->d_pt_b, sim_b, (size_t)n * 4, hipMemcpyDeviceToDevice, st);
-            (void)hipMemcpyAsync(h->d_pt_lb, sim_lb, (size_t)n * 8, hipMemcpyDeviceToDevice, st);
-        }
-#endif
-        if (dim == 3) cl_launch_search<3>(h, n, st, sit_min, xcd_order);
-        else if (dim == 4) cl_launch_search<4>(h, n, st, sit_min, xcd_order);
-        else cl_launch_search<5>(h, n, st, sit_min, xcd_order);
-#ifdef VG_DEV
-        if (r == 1 && getenv("VG_CLUSTER_SEEDSIM")) {
-            (void)hipMemsetAsync(h->d_counter + 5, 0, 4, st);
-            hipLaunchKernelGGL(k_cl_seedsim_drop, dim3(nb), dim3(256), 0, st, n, h->d_core2, h->d_pt_w, h->d_pt_b, h->d_counter);
-            hipLaunchKernelGGL(k_cl_b_round_init, dim3(nb), dim3(256), 0, st, n, h->d_comp, h->d_best_w, h->d_best_d, h->d_best_e, h->d_sel_a, flags, h->d_csize, h->d_giant, h->d_code_s, h->d_cell_comp);
-            hipLaunchKernelGGL(k_cl_b_seed, dim3(nb), dim3(256), 0, st, n, h->d_comp, h->d_pt_b, h->d_pt_w, h->d_best_w, flags);
-            hipLaunchKernelGGL(k_cl_b_purity, dim3(nb), dim3(256), 0, st, n, h->d_code_s, h->d_comp, h->d_cell_comp, flags);   // (round_init rewrote the pure values)
-            if (dim == 3) cl_launch_search<3>(h, n, st, sit_min, xcd_order);          // walks only the points that were not seedable
-            else if (dim == 4) cl_launch_search<4>(h, n, st, sit_min, xcd_order);
-            else cl_launch_search<5>(h, n, st, sit_min, xcd_order);
-            int left = 0;
-            (void)hipMemcpyAsync(&left, h->d_counter + 5, 4, hipMemcpyDeviceToHost, st);
-            (void)hipStreamSynchronize(st);
-            fprintf(stderr, "[cluster seedsim] round 1: %d of %d points have no edge at their own core distance (the second k_cl_b_search launch walks only these)\n", left, n);
-        }
+#ifdef VG_DEV      // the walk at the workgroup size asked for, inside the simulations that run a round's search twice
+        cl_dev_round_search<DIM>(h, n, st, r, sw);
+#else
+        cl_launch_walk<DIM, 512>(h, n, st, sw.sit_min, sw.xcd_order);
 #endif
         hipLaunchKernelGGL(k_cl_b_select_d, dim3(nb), dim3(256), 0, st, n, h->d_comp, h->d_best_w, h->d_pt_w, h->d_pt_d, h->d_best_d, flags);
         hipLaunchKernelGGL(k_cl_b_select, dim3(nb), dim3(256), 0, st, n, h->d_comp, h->d_best_w, h->d_best_d, h->d_pt_w, h->d_pt_d,
                            h->d_pt_key, h->d_best_e, flags);
         hipLaunchKernelGGL(k_cl_b_pick, dim3(nb), dim3(256), 0, st, n, h->d_comp, h->d_best_w, h->d_best_d, h->d_best_e, h->d_pt_w,
-                           h->d_pt_d, h->d_pt_key, h->d_pt_b, h->d_sel_a, h->d_sel_b, flags, h->d_giant, sit_min);
+                           h->d_pt_d, h->d_pt_key, h->d_pt_b, h->d_sel_a, h->d_sel_b, flags, h->d_giant, sw.sit_min);
         hipLaunchKernelGGL(k_cl_b_emit, dim3(nb), dim3(256), 0, st, n, h->d_comp, h->d_sel_a, h->d_sel_b, h->d_best_w,
                            h->d_perm, h->d_parent2, h->d_counter, h->d_mst_a, h->d_mst_b, h->d_mst_w, flags);
         hipLaunchKernelGGL(k_cl_b_compress, dim3(nb), dim3(256), 0, st, n, h->d_comp, h->d_parent2, flags, h->d_aux, h->d_csize, h->d_giant);
         return hipMemcpyAsync(h->h_counter + ((r - 1) & 15), h->d_counter, 4, hipMemcpyDeviceToHost, st);
     };
     while (edges < n - 1) {
-        const int batch = (rounds == 0 && !h->d_dbg) ? first_batch : 1;
+        const int batch = (rounds == 0 && !h->d_dbg) ? sw.first_batch : 1;
         const int first = rounds + 1;
         for (int b = 0; b < batch; ++b) {
             if (++rounds > 64) {
@@ -2037,13 +1685,9 @@ int vg_cluster_mst_nd(vg_cluster* h, const float* d_points, int n, int stride, i
         for (int r = first; r <= rounds; ++r) {
             const int e = h->h_counter[(r - 1) & 15];
             if (h->d_dbg) {
-                std::vector<int> sc(n);
-                (void)hipMemcpy(sc.data(), h->d_dbg, 4 * (size_t)n, hipMemcpyDeviceToHost);
-                std::sort(sc.begin(), sc.end());
-                long long tot = 0; int active = 0;
-                for (int v : sc) { tot += v; active += v > 0; }
+                const ClDbgCounts sc = cl_dbg_counts(h, n, st);
                 fprintf(stderr, "[cluster dbg] round %d: edges %d -> %d, searching threads %d, scanned points: total %lld, median %d, p99 %d, p99.9 %d, max %d\n",
-                        r, edges, e, active, tot, sc[n / 2], sc[(size_t)n * 99 / 100], sc[(size_t)n * 999 / 1000], sc[n - 1]);
+                        r, edges, e, sc.nonzero, sc.total, sc.at(1, 2), sc.at(99, 100), sc.at(999, 1000), sc.max());
             }
             if (e == edges && !needed) {
                 fprintf(stderr, "[vilgod_hip] vg_cluster_mst: no progress in round %d (%d of %d edges)\n", r, e, n - 1);
@@ -2070,6 +1714,30 @@ int vg_cluster_mst_nd(vg_cluster* h, const float* d_points, int n, int stride, i
     if (d_mst_w2) VG_CHECK(hipMemcpyAsync(d_mst_w2, h->d_mst_w_s, 8 * (size_t)m, hipMemcpyDeviceToDevice, st));
     VG_LAUNCH_CHECK();
     return VG_OK;
+}
+
+extern "C" {
+
+/* Exact core distances + exact MST of the mutual reachability graph.  SYNCHRONOUS on `stream` (one small
+ * device->host counter read per Boruvka round).
+ *   d_points [n,stride] f32; dim = 3, 4 or 5 leading columns form the clustering space (x,y,z first: the cell grid and
+ *   all pruning bounds use x,y,z only -- a lower bound of the dim-D distance; 5-D = the two-frame input of
+ *   zero_shot_detector.py:232-237: x,y,z,entropy,0.1*frame).  Distances: float64, summed left to right.
+ *   k = min_samples (1 .. VG_CLUSTER_MAX_K): core = distance to the k-th nearest OTHER point (k <= 15: register lists,
+ *   k >= 16: ClLdsHeap / the WIDE form of k_cl_core_far)
+ *   d_core2  [n] f64 squared core distances, ORIGINAL point order (may be NULL)
+ *   d_mst_lo/hi [n-1] int32 original point ids (lo < hi), d_mst_w2 [n-1] f64 squared weights, sorted ascending by
+ *   weight (equal weights in unspecified order: vg_hdbscan_tree_host callers sort ties by (lo,hi)).
+ *   h_rounds: number of Boruvka rounds (diagnostic, may be NULL). */
+int vg_cluster_mst_nd(vg_cluster* h, const float* d_points, int n, int stride, int dim, int k, double* d_core2,
+                      int32_t* d_mst_lo, int32_t* d_mst_hi, double* d_mst_w2, int32_t* h_rounds, void* stream) {
+    if (!h || !d_points || n < 0 || dim < 3 || dim > 5 || stride < dim || k < 1 || k > VG_CLUSTER_MAX_K) return VG_ERR_ARG;
+    if (n > h->max_points) return VG_ERR_CAPACITY;
+    if (h_rounds) *h_rounds = 0;
+    if (n < 2) return VG_OK;
+    return cl_with_dim(dim, [&](auto d) {
+        return cl_mst<decltype(d)::value>(h, d_points, n, stride, k, d_core2, d_mst_lo, d_mst_hi, d_mst_w2, h_rounds, (hipStream_t)stream);
+    });
 }
 
 int vg_cluster_mst(vg_cluster* h, const float* d_points, int n, int stride, int k, double* d_core2, int32_t* d_mst_lo,
