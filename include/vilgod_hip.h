@@ -247,7 +247,8 @@ void vg_ground_default_params(vg_ground_params* p);          /* patchworkpp.h:75
 int vg_ground_create(vg_ground** out, const vg_ground_params* p, int max_points);   /* patchworkpp.h:116-146 */
 void vg_ground_destroy(vg_ground* h);
 /* fresh adaptive state (the reference builds a new object per sequence, zero_shot_detector.py:137-140);
- * p may be NULL to keep the parameters. */
+ * p may be NULL to keep the parameters.  Parameters that vg_ground_create refuses are refused here too (VG_ERR_ARG):
+ * the handle then keeps its parameters and its state. */
 int vg_ground_reset(vg_ground* h, const vg_ground_params* p);
 /* estimateGround + getGround (patchworkpp.cpp:152-337; pybinding.cpp:49,53).  d_points: [n,stride] f32,
  * columns x, y, z, intensity; z_offset is subtracted in float64 and rounded to float32 exactly as

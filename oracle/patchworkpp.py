@@ -58,6 +58,7 @@ def load():
         _lib.pw_eig3.argtypes = [ctypes.c_void_p] * 3
         _lib.pw_default_params.argtypes = [ctypes.c_void_p]
         _lib.pw_set_numeric_model.argtypes = [ctypes.c_void_p, ctypes.c_int]
+        _lib.pw_get_counts.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
     return _lib
 
 
@@ -101,6 +102,16 @@ class patchworkpp:
         self._lib.pw_get_state(self._h, out.ctypes.data)
         return dict(sensor_height=out[0], elevation_thr=out[1:5].copy(), flatness_thr=out[5:9].copy(),
                     n_elevation=out[9:13].astype(int), n_flatness=out[13:17].astype(int))
+
+    def counts(self):
+        """Reach counters of the last frame (pw_get_counts): which branches it took.  `appended` counts since creation."""
+        c = np.zeros(28, dtype=np.int64)
+        self._lib.pw_get_counts(self._h, c.ctypes.data)
+        gle = dict(zip(('not_upright', 'far_accepted', 'heading_inside', 'near_by_elevation', 'near_by_flatness', 'candidate'), c[4:10].tolist()))
+        tgr = dict(zip(('reverted_sigmoid', 'reverted_1500', 'rejected_sigmoid', 'rejected_line'), c[10:14].tolist()))
+        return dict(rnr_rejected=int(c[0]), rvpf_patches=int(c[1]), rvpf_killed=int(c[2]), rvpf_far_vertical=int(c[3]), gle=gle, tgr=tgr,
+                    rings_carry=int(c[14]), rings_after_clear=int(c[15]), appended=c[16:20].copy(),
+                    evicted_elev=c[20:24].copy(), evicted_flat=c[24:28].copy())
 
     def getHeight(self):
         return self.state()['sensor_height']

@@ -265,6 +265,21 @@ void calc_mean_stdev(const std::vector<double>& v, double& mean, double& stdev) 
 
 struct PatchPt { float x, y, z; int idx; };
 
+// Reach counters (pw_get_counts): which branches the last frame took.  They are written beside the algorithm and read by nothing in it.
+struct Counts {
+    long long rnr_rejected;                 // points taken out by RNR
+    long long rvpf_patches, rvpf_killed;    // patches where R-VPF removed at least one point / points it removed
+    long long rvpf_far_vertical;            // patches outside zone 0 whose R-VPF fit was not upright: fitted once, nothing removed
+    long long gle[6];                       // patches: not upright, far ring accepted, heading inside, near accepted by elevation,
+                                            // near accepted by flatness only, TGR candidate
+    long long tgr[4];                       // candidates: reverted by the sigmoid, reverted only by the `> 1500` rule, rejected by the
+                                            // sigmoid, rejected only by line_variable (each names the test that DECIDED the outcome)
+    long long rings_carry;                  // rings with candidates while ringwise_flatness held values of an earlier candidate-free ring
+    long long rings_after_clear;            // rings with candidates right after a ring that cleared ringwise_flatness
+    long long appended[4];                  // per near ring: values appended to its stores since creation
+    long long evicted_elev[4], evicted_flat[4];   // per near ring: values evicted this frame
+};
+
 struct Candidate { int concentric_idx, sector_idx; double flatness, line_variable; std::vector<int> ground; };
 
 struct Oracle {
@@ -275,6 +290,7 @@ struct Oracle {
     std::vector<float> patch_info;
     int numeric_model = 0;     // 0: float64 SUM256 one-pass (what the HIP kernels reproduce); 1 / 2: float32 two-pass, scalar / 8-lane order
     std::vector<float> sel;    // the selected points of one plane fit (models 1 / 2)
+    Counts tally{};
 
     explicit Oracle(const PwParams& pp) : p(pp) {           // patchworkpp.h:116-146
         double z2 = (7 * p.min_range + p.max_range) / 8.0;
@@ -311,6 +327,11 @@ struct Oracle {
 
     void estimate(const float* pts, int n, int stride, uint8_t* ground_mask) {
         memset(ground_mask, 0, (size_t)n);
+        {
+            Counts fresh{};
+            memcpy(fresh.appended, tally.appended, sizeof(fresh.appended));      // the only tally that outlives a frame
+            tally = fresh;
+        }
         int patch_base[4], n_patches = 0;
         for (int k = 0; k < 4; ++k) { patch_base[k] = n_patches; n_patches += p.num_rings_each_zone[k] * p.num_sectors_each_zone[k]; }
         std::vector<std::vector<PatchPt>> patches(n_patches);
@@ -326,7 +347,7 @@ struct Oracle {
             double r = (double)(float)sqrt((double)rr);
                 double zd = z;
                 double ang = atan2(zd, r) * 180 / M_PI;
-                if (ang < p.RNR_ver_angle_thr && zd < -p.sensor_height - 0.8 && (double)inten < p.RNR_intensity_thr) continue;  // noise -> non-ground
+                if (ang < p.RNR_ver_angle_thr && zd < -p.sensor_height - 0.8 && (double)inten < p.RNR_intensity_thr) { tally.rnr_rejected++; continue; }  // noise -> non-ground
             }
             if (z == FLT_MIN) continue;                                              // :592
             double xd = x, yd = y;
@@ -345,9 +366,11 @@ struct Oracle {
         int concentric_idx = 0;
         std::vector<Candidate> candidates;
         std::vector<double> ringwise_flatness;
+        bool prev_ring_cleared = false;
         Acc256* acc = new Acc256();
         for (int zone = 0; zone < p.num_zones; ++zone) {
             for (int ring = 0; ring < p.num_rings_each_zone[zone]; ++ring) {
+                const size_t carried = ringwise_flatness.size();
                 for (int sector = 0; sector < p.num_sectors_each_zone[zone]; ++sector) {
                     const int pid = patch_base[zone] + ring * p.num_sectors_each_zone[zone] + sector;
                     std::vector<PatchPt>& P = patches[pid];
@@ -361,6 +384,7 @@ struct Oracle {
                     std::vector<char> alive(np, 1);
                     // ---- extract_piecewiseground, :468-550 ----
                     if (p.enable_RVPF) {
+                        long long killed = 0;
                         for (int it = 0; it < p.num_iter; ++it) {
                             double thr = seed_threshold(zone, P, alive, p.th_seeds_v);
                             acc->clear(); int cnt = 0;
@@ -374,9 +398,14 @@ struct Oracle {
                             if (numeric_model) estimate_plane_f32(sel, numeric_model, pl); else estimate_plane(acc->finish(), cnt, pl);
                             if (zone == 0 && (double)pl.normal[2] < p.uprightness_thr) {
                                 for (int i = 0; i < np; ++i)
-                                    if (alive[i] && fabs(plane_dist(pl, P[i].x, P[i].y, P[i].z)) < p.th_dist_v) alive[i] = 0;
-                            } else break;
+                                    if (alive[i] && fabs(plane_dist(pl, P[i].x, P[i].y, P[i].z)) < p.th_dist_v) { alive[i] = 0; killed++; }
+                            } else {
+                                if (zone != 0 && (double)pl.normal[2] < p.uprightness_thr) tally.rvpf_far_vertical++;
+                                break;
+                            }
                         }
+                        tally.rvpf_killed += killed;
+                        if (killed) tally.rvpf_patches++;
                     }
                     {
                         double thr = seed_threshold(zone, P, alive, p.th_seeds);
@@ -421,6 +450,7 @@ struct Oracle {
                         is_flat = flatness < p.flatness_thr[concentric_idx];
                     }
                     if (is_upright && not_elevated && is_near) {
+                        tally.appended[concentric_idx]++;
                         upd_elev[concentric_idx].push_back(elevation);
                         upd_flat[concentric_idx].push_back(flatness);
                         ringwise_flatness.push_back(flatness);
@@ -431,6 +461,7 @@ struct Oracle {
                     else if (!heading_outside) decision = 0;
                     else if (not_elevated || is_flat) decision = 1;
                     else decision = 2;
+                    tally.gle[!is_upright ? 0 : !is_near ? 1 : !heading_outside ? 2 : not_elevated ? 3 : is_flat ? 4 : 5]++;
                     info[1] = (float)dst.size();
                     for (int i = 0; i < 3; ++i) { info[2 + i] = pl.normal[i]; info[5 + i] = pl.mean[i]; info[8 + i] = pl.sv[i]; }
                     info[11] = (float)decision;
@@ -439,23 +470,28 @@ struct Oracle {
                 }
                 // ---- TGR, :293-305, :403-465 ----
                 if (!candidates.empty()) {
+                    if (carried > 0) tally.rings_carry++;
+                    if (prev_ring_cleared) tally.rings_after_clear++;
                     if (p.enable_TGR) {
                         double mean_f = 0.0, std_f = 0.0;
                         calc_mean_stdev(ringwise_flatness, mean_f, std_f);
                         for (const Candidate& c : candidates) {
                             double mu = mean_f + 1.5 * std_f;
                             double prob = 1 / (1 + exp((c.flatness - mu) / (mu / 10)));
+                            const bool by_sigmoid = prob > 0.5;
                             if (c.ground.size() > 1500 && c.flatness < p.th_dist * p.th_dist) prob = 1.0;
                             double prob_line = 1.0;
                             if (c.line_variable > 8.0) prob_line = 0.0;
                             bool revert = prob_line * prob > 0.5;
+                            tally.tgr[revert ? (by_sigmoid ? 0 : 1) : (prob > 0.5 ? 3 : 2)]++;
                             if (concentric_idx < p.num_rings_of_interest && revert)
                                 for (int id : c.ground) ground_mask[id] = 1;
                         }
                     }
                     candidates.clear();
                     ringwise_flatness.clear();
-                }
+                    prev_ring_cleared = true;
+                } else prev_ring_cleared = false;
                 concentric_idx++;
             }
         }
@@ -468,7 +504,7 @@ struct Oracle {
             if (i == 0) { p.elevation_thr[i] = m + 3 * s; p.sensor_height = -m; }
             else p.elevation_thr[i] = m + 2 * s;
             int exceed = (int)upd_elev[i].size() - p.max_elevation_storage;
-            if (exceed > 0) upd_elev[i].erase(upd_elev[i].begin(), upd_elev[i].begin() + exceed);
+            if (exceed > 0) { tally.evicted_elev[i] = exceed; upd_elev[i].erase(upd_elev[i].begin(), upd_elev[i].begin() + exceed); }
         }
         // ---- update_flatness_thr, :360-376 (note the `break`s) ----
         for (int i = 0; i < p.num_rings_of_interest; ++i) {
@@ -478,7 +514,7 @@ struct Oracle {
             calc_mean_stdev(upd_flat[i], m, s);
             p.flatness_thr[i] = m + s;
             int exceed = (int)upd_flat[i].size() - p.max_flatness_storage;
-            if (exceed > 0) upd_flat[i].erase(upd_flat[i].begin(), upd_flat[i].begin() + exceed);
+            if (exceed > 0) { tally.evicted_flat[i] = exceed; upd_flat[i].erase(upd_flat[i].begin(), upd_flat[i].begin() + exceed); }
         }
     }
 };
@@ -510,6 +546,13 @@ void pw_get_state(void* h, double* out17) {
     out17[0] = o->p.sensor_height;
     for (int i = 0; i < 4; ++i) { out17[1 + i] = o->p.elevation_thr[i]; out17[5 + i] = o->p.flatness_thr[i]; }
     for (int i = 0; i < 4; ++i) { out17[9 + i] = (double)o->upd_elev[i].size(); out17[13 + i] = (double)o->upd_flat[i].size(); }
+}
+
+/* reach counters of the last frame (struct Counts, 28 values): rnr_rejected, rvpf_patches, rvpf_killed, rvpf_far_vertical, gle[6], tgr[4], rings_carry,
+ * rings_after_clear, appended[4] (since creation), evicted_elev[4], evicted_flat[4] */
+void pw_get_counts(void* h, long long* out28) {
+    static_assert(sizeof(Counts) == 28 * sizeof(long long), "Counts is 28 tallies");
+    memcpy(out28, &((Oracle*)h)->tally, sizeof(Counts));
 }
 
 int pw_num_patches(void* h) {

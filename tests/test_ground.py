@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 import torch
 
+from ground_ref import _same_sequence          # kernel == oracle, frame after frame (shared with test_ground_edges.py)
 from oracle import patchworkpp as opw
 from vilgod_amd import synthetic
 
@@ -161,30 +162,6 @@ def test_hip_ground_rnr_radius_is_the_float_root(cuda):
     assert m.shape == (len(pts),)
     assert not m[first:][noise].any()
     assert m[first:][~noise].sum() >= 8
-
-
-def _same_sequence(frames, z_offset, cuda, min_range=1.5, tweak=None):
-    from vilgod_amd import patchworkpp as gpw
-    po, pg = opw.Parameters(), gpw.Parameters()
-    for p in (po, pg):
-        p.min_range = min_range
-        if tweak:
-            tweak(p)
-    oracle = opw.patchworkpp(po)
-    gpu = gpw.patchworkpp(pg, max_points=max(len(f) for f in frames) + 1, device=cuda)
-    for k, pts in enumerate(frames):
-        want = np.sort(opw.mask_ground_points(pts, oracle, z_offset))
-        got = np.sort(gpw.mask_ground_points_patchwork_pp(pts, gpu, z_offset))
-        assert np.array_equal(want, got), (k, len(want), len(got), len(np.setxor1d(want, got)))
-        so, sg = oracle.state(), gpu.state()
-        assert so['sensor_height'] == sg['sensor_height'], k
-        assert np.array_equal(so['elevation_thr'], sg['elevation_thr']) and np.array_equal(so['flatness_thr'], sg['flatness_thr'])
-        assert np.array_equal(so['n_elevation'], sg['n_elevation']) and np.array_equal(so['n_flatness'], sg['n_flatness'])
-        io, ig = oracle.patch_info(), gpu.patch_info()
-        assert np.array_equal(io[:, :2], ig[:, :2]), k                       # sizes and inlier counts per patch
-        live = io[:, 0] >= 10
-        assert np.array_equal(io[live, 2:11], ig[live, 2:11], equal_nan=True), k   # normals, means, singular values: bit exact
-    return gpu
 
 
 @pytest.mark.gpu

@@ -719,17 +719,21 @@ static int pw_upload(vg_ground* h) {
     return VG_OK;
 }
 
-int vg_ground_create(vg_ground** out, const vg_ground_params* p, int max_points) {
-    if (!out || !p || max_points <= 0) return VG_ERR_ARG;
+// What the kernels' fixed-size arrays can hold (sh_rf[4][64], hist[PW_MAX_PATCHES], one lane per ring, the ring buffers of PwState):
+// every way parameters reach a handle -- vg_ground_create, vg_ground_reset -- goes through this.
+static bool pw_params_ok(const vg_ground_params* p) {
     int np = 0, nr = 0;
     for (int k = 0; k < 4; ++k) {
         np += p->num_rings_each_zone[k] * p->num_sectors_each_zone[k];
         nr += p->num_rings_each_zone[k];
-        if (p->num_sectors_each_zone[k] > 64 || p->num_sectors_each_zone[k] <= 0) return VG_ERR_ARG;
+        if (p->num_sectors_each_zone[k] > 64 || p->num_sectors_each_zone[k] <= 0) return false;
     }
-    if (np > PW_MAX_PATCHES || nr > 64 || p->num_zones != 4 || p->num_rings_of_interest > 4 ||
-        p->max_elevation_storage + 64 > PW_STORE_CAP || p->max_flatness_storage + 64 > PW_STORE_CAP)
-        return VG_ERR_ARG;
+    return !(np > PW_MAX_PATCHES || nr > 64 || p->num_zones != 4 || p->num_rings_of_interest > 4 ||
+             p->max_elevation_storage + 64 > PW_STORE_CAP || p->max_flatness_storage + 64 > PW_STORE_CAP);
+}
+
+int vg_ground_create(vg_ground** out, const vg_ground_params* p, int max_points) {
+    if (!out || !p || max_points <= 0 || !pw_params_ok(p)) return VG_ERR_ARG;
     vg_ground* h = new vg_ground();
     memset(h, 0, sizeof(*h));
     h->p = *p;
@@ -761,7 +765,10 @@ void vg_ground_destroy(vg_ground* h) {
 
 int vg_ground_reset(vg_ground* h, const vg_ground_params* p) {
     if (!h) return VG_ERR_ARG;
-    if (p) h->p = *p;
+    if (p) {
+        if (!pw_params_ok(p)) return VG_ERR_ARG;     // refused: the handle keeps its parameters and its state
+        h->p = *p;
+    }
     return pw_upload(h);
 }
 

@@ -60,10 +60,9 @@ class patchworkpp:
 
     def reset(self, params=None):
         """New sequence: fresh adaptive state (the reference constructs a new object)."""
-        if params is not None:
+        check(lib.vg_ground_reset(self._h, ctypes.byref(params) if params is not None else None), 'vg_ground_reset')
+        if params is not None:          # a refused set leaves the handle, and this object, on the previous one
             self._params = params
-        check(lib.vg_ground_reset(self._h, ctypes.byref(self._params) if params is not None else None),
-              'vg_ground_reset')
 
     # -- zero-copy path -----------------------------------------------------------------------------
     def estimate_mask(self, points, z_offset=0.0, out=None, stream=None):
