@@ -135,14 +135,19 @@ int vg_vit_profile_read_kind(vg_vit* v, int kind, int32_t* h_launches, double* h
 
 /* One projection GEMM of the tower, C = X @ Wt^T with the fused epilogue the block uses
  * (model.py:175-191: in_proj, out_proj + residual, c_fc + QuickGELU, c_proj + residual), exposed so the
- * GEMM can be unit-tested and timed alone.  dtype 1: f16 operands (M%256, N%128, K%64 == 0); 0: f32
+ * GEMM can be unit-tested and timed alone.  dtype 1: f16 operands (M%256, N%128, K%32 == 0); 0: f32
  * (M%64, N%64, K%16).  epi 0: +bias -> C   1: +bias, QuickGELU -> C   2: d_resid(f32) += X@Wt^T + bias
  * 3: C float32, no bias (patch embedding, model.py:224).
- * 4 (dtype 1, N%256 == 0, K%64 == 0): d_resid points to an fp16 [M,N] residual stream updated in place,
+ * 4 (dtype 1, N%256 == 0, K%64 == 0, K >= 128): d_resid points to an fp16 [M,N] residual stream updated in place,
  *   resid = f16(resid + f16(X@Wt^T + bias)) -- what the reference's fp16 run computes; the f16 tower takes it only with the
  *   environment variable VG_VIT_RESID16=1 (width%256 == 0); the default keeps the fp32 stream of epi 2. */
 int vg_gemm(int dtype, int epi, const void* d_X, const void* d_Wt, const float* d_bias, void* d_C, float* d_resid,
             int M, int N, int K, void* stream);
+/* The kernel vg_gemm would launch for these arguments under the current environment switches (VG_GEMM_W4, VG_GEMM_F32_MFMA, read
+ * per call as vg_gemm reads them): 0 k_gemm_f16, 1 k_gemm_f16_pp64, 2 k_gemm_f16_w4, 3 k_gemm_f32, 4 k_gemm_f32_mfma; negative where
+ * vg_gemm returns VG_ERR_ARG.  It is the function vg_gemm's own dispatch asks; it launches nothing and touches no device.  (The
+ * split-K tail of vg_gemm_resid_splitk is planned from the CU count and is not part of the answer.) */
+int vg_gemm_family(int dtype, int epi, int M, int N, int K);
 
 /* The folded-LayerNorm epilogues of the fp16 projection GEMM (model.py:190-191: ln_1 / ln_2 ride in in_proj / c_fc), alone, for
  * unit tests.  Handle-less like vg_gemm: the kernel family is chosen by VG_GEMM_W4, read per call.  d_X, d_Wt f16; M % 256 == 0,

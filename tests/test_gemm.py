@@ -21,7 +21,7 @@ def _ref(X, W, bias, resid, epi):
 @pytest.mark.parametrize('dtype', [1, 0])
 @pytest.mark.parametrize('epi', [0, 1, 2, 3])
 @pytest.mark.parametrize('shape', [(256, 128, 64), (512, 768, 768), (256, 2304, 768), (256, 768, 3072), (768, 128, 128), (512, 3072, 768), (256, 1536, 96),
-                                   (512, 512, 160), (256, 256, 128)])     # K % 64 != 0 -> k_gemm_f16_pp16; two K-tiles -> the shortest pp64 loop
+                                   (512, 512, 160), (256, 256, 128)])     # K % 64 != 0 -> k_gemm_f16; two K-tiles -> the shortest pp64 loop (which kernel runs: vg_gemm_family, test_gemm_families.py)
 def test_gemm_epilogues(cuda, dtype, epi, shape):
     from vilgod_amd._lib import lib, ptr, stream_ptr, check
     M, N, K = shape
@@ -201,6 +201,20 @@ def test_gemm_w4_equals_pp64_bit_for_bit(cuda, epi, shape, monkeypatch):
         err = (outs[0][rows].double() - want).abs().max().item()
         print(f'w4 == pp64 {shape} epi {epi}: {len(rows)} sampled rows within {err:.2e} of float64')
         assert err < 3e-3 * max(1.0, want.abs().max().item())
+        if shape == (66560, 256, 256):
+            # the same launch on integers (gemm_ref.operands 'integer': every partial sum exact in fp32 in any order), the same sampled rows,
+            # the float64 product on the GPU: a K element dropped or taken twice by a second or later tile fails with zero tolerance
+            import gemm_ref as G
+            assert lib.vg_gemm_family(1, epi, M, N, K) == G.FAMILY_CODES['w4']
+            o = G.operands('integer', M, N, K, 1).to(cuda)
+            C = torch.full((M, N), float('nan'), dtype=torch.float32 if epi == 3 else torch.float16, device=cuda)
+            R = o.resid.clone()
+            check(lib.vg_gemm(1, epi, ptr(o.X), ptr(o.W), ptr(o.bias), ptr(C), ptr(R), M, N, K, stream_ptr()))
+            torch.cuda.synchronize()
+            got = R if epi == 2 else C
+            assert torch.isfinite(got.float()).all()               # (all rows: no tile left unwritten)
+            ratio, _, _ = G.check_case(got[rows], o.rows(rows), epi, 'w4')
+            print(f'w4 {shape} epi {epi} integer: {len(rows)} sampled rows ' + ('exact' if epi != 1 else f'within {ratio:.3f} of the QuickGELU bound'))
 
 
 @pytest.mark.gpu

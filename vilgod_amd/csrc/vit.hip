@@ -61,7 +61,7 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// fp16 MFMA GEMM:  C[m][n] = sum_k X[m][k] * Wt[n][k]  (+ epilogue).  M%128==0, N%128==0, K%64==0.
+// fp16 MFMA GEMM:  C[m][n] = sum_k X[m][k] * Wt[n][k]  (+ epilogue).  M%256==0, N%128==0, K%32==0.
 // The MFMA computes the TRANSPOSED tile (A operand = weight rows, B operand = activation rows) so a
 // lane owns one output row m and 4-wide runs of consecutive n: vector loads/stores in the epilogue.
 #define GBM 256                             // block tile: 256 (tokens) x 128 (features), K-step 32
@@ -2372,16 +2372,38 @@ static int launch_gemm_resid_tail(const void* X, const void* Wt, const float* bi
 #include "dev/vit_dev_launchers.inc"
 #endif  // VG_DEV
 
-// Every projection GEMM of the tower and of the test entry points.  fp16, top to bottom: the two fp16-stream epilogues (one kernel family
-// each), then for the ViT shapes (N % 256 == 0, K >= 128) the split-K tail, k_gemm_f16_w4, k_gemm_f16_pp64; k_gemm_f16 serves the
-// remaining legal shapes.  fp32: the MFMA kernel where its tile divides the shape, else the vector-ALU kernel.
+// Which kernel a projection GEMM runs on: the ONE place the choice is made (launch_gemm asks it and launches; vg_gemm_family hands
+// the answer to the tests).  fp16, top to bottom: the two fp16-stream epilogues (one kernel family each), then for the ViT shapes
+// (gemm_tile256: N % 256 == 0, K >= 128) k_gemm_f16_w4 from four K-tiles up, else k_gemm_f16_pp64; k_gemm_f16 serves the remaining
+// legal shapes.  fp32: the MFMA kernel where its tile divides the shape, else the vector-ALU kernel.  Negative: no kernel takes the
+// shape (VG_ERR_ARG).  Host arithmetic only.  (The split-K tail of a k_gemm_f16_pp64 launch is launch_gemm's own: it needs the CU count.)
+enum { GF_F16 = 0, GF_PP64 = 1, GF_W4 = 2, GF_F32 = 3, GF_F32_MFMA = 4, GF_REFUSED = -1 };
+static bool gemm_tile256(int dtype, int N, int K) { return dtype == 1 && N % 256 == 0 && K % 64 == 0 && K / 64 >= 2; }
+static int gemm_family(int dtype, int epi, int M, int N, int K, int gemm_w4, bool f32_mfma, bool use_pp) {
+    const bool w4 = gemm_w4 && K / 64 >= 4;        // (k_gemm_f16_w4's ring wants four K-tiles)
+    if (epi == EPI_BIAS_RESID_HL)                  // the stream as an fp16 pair: k_gemm_f16_w4's producer epilogue only
+        return use_pp && w4 && M % 256 == 0 ? GF_W4 : GF_REFUSED;
+    if (epi == EPI_BIAS_RESID_H)                   // fp16 residual stream: only k_gemm_f16_pp64 implements it
+        return use_pp && M % 256 == 0 ? GF_PP64 : GF_REFUSED;
+    if (epi < EPI_BIAS || epi > EPI_NONE_F32) return GF_REFUSED;
+    if (dtype == 1) {
+        if (M % GBM || N % GBN || K % GK) return GF_REFUSED;
+        if (use_pp) return w4 ? GF_W4 : GF_PP64;
+        return GF_F16;
+    }
+    if (M % 64 || N % 64 || K % 16) return GF_REFUSED;
+    return M % 128 == 0 && N % 128 == 0 && f32_mfma ? GF_F32_MFMA : GF_F32;     // (VG_GEMM_F32_MFMA=0: the vector-ALU kernel for every shape, bit-identical)
+}
+
+// Every projection GEMM of the tower and of the test entry points: the kernel gemm_family names, and for the residual GEMMs of the
+// k_gemm_f16_pp64 family the split-K tail where scratch is at hand.
 template <int EPI, int LN = 0>
 static int launch_gemm(const vg_vit* cv, const void* X, const void* Wt, const float* bias, void* C, float* resid, int M,
                        int N, int K, hipStream_t st, int ldc = 0, const float* ln_c1 = nullptr, LnPartial* ln_stats = nullptr,
                        f16* ln_x16 = nullptr, float* sk_scratch = nullptr, size_t sk_bytes = 0) {
     if (ldc == 0) ldc = N;
     vg_vit* v = const_cast<vg_vit*>(cv);
-    bool use_pp = v->dtype == 1 && N % 256 == 0 && K % 64 == 0 && K / 64 >= 2;
+    bool use_pp = gemm_tile256(v->dtype, N, K);
     const bool prof = v->prof_on && v->prof_n < VG_PROF_MAX;
     if (prof) (void)hipEventRecord(v->prof_ev[2 * v->prof_n], st);
     struct Closer {
@@ -2398,44 +2420,41 @@ static int launch_gemm(const vg_vit* cv, const void* X, const void* Wt, const fl
     { const int rc = dev_launch_gemm<EPI, LN>(v, X, Wt, bias, C, resid, M, N, K, st, ldc, ln_c1, ln_stats, ln_x16, &use_pp); if (rc != VG_DEV_PASS) return rc; }
     closer.kind = use_pp ? 1 : 0;
 #endif
-    const bool w4 = v->gemm_w4 && K / 64 >= 4;        // (k_gemm_f16_w4's ring wants four K-tiles)
-    if constexpr (EPI == EPI_BIAS_RESID_HL) {     // the stream as an fp16 pair: k_gemm_f16_w4's producer epilogue only
-        if (!(LN == 2 && use_pp && w4 && M % 256 == 0 && resid && ln_x16)) return VG_ERR_ARG;
+    const int fam = gemm_family(v->dtype, EPI, M, N, K, v->gemm_w4, v->f32_mfma, use_pp);
+    if (fam < 0) return VG_ERR_ARG;
+    if constexpr (EPI == EPI_BIAS_RESID_HL) {
+        if (!(LN == 2 && resid && ln_x16)) return VG_ERR_ARG;
         return launch_gemm_w4<EPI, LN>(X, Wt, bias, C, resid, M, N, K, ldc, st, ln_c1, ln_stats, ln_x16);
-    } else if constexpr (EPI == EPI_BIAS_RESID_H) {      // fp16 residual stream: only k_gemm_f16_pp64 implements it
-        if (!use_pp) return VG_ERR_ARG;
+    } else if constexpr (EPI == EPI_BIAS_RESID_H) {
         return launch_gemm_pp64<EPI>(X, Wt, bias, C, resid, M, N, K, ldc, st);
-    } else if (v->dtype == 1) {
-        if (M % GBM || N % GBN || K % GK) return VG_ERR_ARG;
-        if (use_pp) {
-            if constexpr (EPI == EPI_BIAS_RESID && LN != 1) {
-                // residual GEMMs with scratch at hand: the row tiles beyond the last complete round of tiles run K-split
-                // (not k_gemm_f16_w4's: persistent workgroups have no tile rounds to fill)
-                if (sk_scratch && M % 256 == 0 && !w4) {
-                    const SplitPlan sp = splitk_plan(M / 256, N / 256, K / 64, sk_bytes, v->splitk_max, vg_cu_count());
-                    if (sp.parts) {
-                        const int rc = launch_gemm_pp64<EPI, false, false, LN>(X, Wt, bias, C, resid, sp.r_main * 256, N, K, ldc, st, nullptr, ln_c1, ln_stats, ln_x16);
-                        if (rc) return rc;
-                        return launch_gemm_resid_tail<LN>(X, Wt, bias, resid, sp.r_main * 256, M - sp.r_main * 256, N, K, ldc, sp.parts, sk_scratch, st,
-                                                          ln_stats, ln_x16);
-                    }
+    } else if (fam == GF_W4) {
+        return launch_gemm_w4<EPI, LN>(X, Wt, bias, C, resid, M, N, K, ldc, st, ln_c1, ln_stats, ln_x16);
+    } else if (fam == GF_PP64) {
+        if constexpr (EPI == EPI_BIAS_RESID && LN != 1) {
+            // residual GEMMs with scratch at hand: the row tiles beyond the last complete round of tiles run K-split
+            // (not k_gemm_f16_w4's: persistent workgroups have no tile rounds to fill)
+            if (sk_scratch && M % 256 == 0) {
+                const SplitPlan sp = splitk_plan(M / 256, N / 256, K / 64, sk_bytes, v->splitk_max, vg_cu_count());
+                if (sp.parts) {
+                    const int rc = launch_gemm_pp64<EPI, false, false, LN>(X, Wt, bias, C, resid, sp.r_main * 256, N, K, ldc, st, nullptr, ln_c1, ln_stats, ln_x16);
+                    if (rc) return rc;
+                    return launch_gemm_resid_tail<LN>(X, Wt, bias, resid, sp.r_main * 256, M - sp.r_main * 256, N, K, ldc, sp.parts, sk_scratch, st,
+                                                      ln_stats, ln_x16);
                 }
             }
-            if (w4) return launch_gemm_w4<EPI, LN>(X, Wt, bias, C, resid, M, N, K, ldc, st, ln_c1, ln_stats, ln_x16);
-            return launch_gemm_pp64<EPI, false, false, LN>(X, Wt, bias, C, resid, M, N, K, ldc, st, nullptr, ln_c1, ln_stats, ln_x16);
         }
+        return launch_gemm_pp64<EPI, false, false, LN>(X, Wt, bias, C, resid, M, N, K, ldc, st, nullptr, ln_c1, ln_stats, ln_x16);
+    } else if (fam == GF_F16) {
         if (LN != 0) return VG_ERR_ARG;            // the folded LayerNorm exists in the 256 x 256 kernels only
         VG_MAX_DYNAMIC_LDS(k_gemm_f16<EPI>, G_LDS_BYTES);
         hipLaunchKernelGGL((k_gemm_f16<EPI>), dim3((M / GBM) * (N / GBN)), dim3(512), G_LDS_BYTES, st, (const f16*)X, (const f16*)Wt, bias, C,
                            resid, M, N, K, ldc, gemm_chunk_tiles(N, K));
+    } else if (fam == GF_F32_MFMA) {
+        hipLaunchKernelGGL((k_gemm_f32_mfma<EPI>), dim3((M / 128) * (N / 128)), dim3(256), 0, st, (const float*)X, (const float*)Wt, bias,
+                           (float*)C, resid, M, N, K);
     } else {
-        if (M % 64 || N % 64 || K % 16) return VG_ERR_ARG;
-        if (M % 128 == 0 && N % 128 == 0 && v->f32_mfma)        // (VG_GEMM_F32_MFMA=0: the vector-ALU kernel for every shape, bit-identical)
-            hipLaunchKernelGGL((k_gemm_f32_mfma<EPI>), dim3((M / 128) * (N / 128)), dim3(256), 0, st, (const float*)X, (const float*)Wt, bias,
-                               (float*)C, resid, M, N, K);
-        else
-            hipLaunchKernelGGL((k_gemm_f32<EPI>), dim3((M / 64) * (N / 64)), dim3(256), 0, st, (const float*)X, (const float*)Wt, bias,
-                               (float*)C, resid, M, N, K);
+        hipLaunchKernelGGL((k_gemm_f32<EPI>), dim3((M / 64) * (N / 64)), dim3(256), 0, st, (const float*)X, (const float*)Wt, bias,
+                           (float*)C, resid, M, N, K);
     }
     VG_LAUNCH_CHECK();
     return VG_OK;
@@ -3135,9 +3154,9 @@ int vg_attention_rows(int dtype, const void* d_qkv, void* d_out, int n_crops, in
 #endif  // VG_DEV
 
 /* C = X @ Wt^T (+ epilogue), exposed for unit tests / micro-benchmarks of the GEMM itself.
- * dtype 1: X,Wt f16, M%128==0, N%128==0, K%64==0; dtype 0: f32, M%64, N%64, K%16.
+ * dtype 1: X,Wt f16, M%256==0, N%128==0, K%32==0; dtype 0: f32, M%64, N%64, K%16.
  * epi 0: +bias -> C (compute dtype)   1: +bias, QuickGELU -> C   2: resid(f32) += acc + bias   3: C f32, no bias
- * epi 4 (dtype 1, N % 256 == 0, K % 64 == 0): d_resid holds fp16 [M,N]: resid = f16(resid + f16(acc + bias)) */
+ * epi 4 (dtype 1, N % 256 == 0, K % 64 == 0, K >= 128): d_resid holds fp16 [M,N]: resid = f16(resid + f16(acc + bias)) */
 int vg_gemm(int dtype, int epi, const void* d_X, const void* d_Wt, const float* d_bias, void* d_C, float* d_resid,
             int M, int N, int K, void* stream) {
     vg_vit v;
@@ -3151,6 +3170,15 @@ int vg_gemm(int dtype, int epi, const void* d_X, const void* d_Wt, const float* 
         case 4: return dtype == 1 ? launch_gemm<EPI_BIAS_RESID_H>(&v, d_X, d_Wt, d_bias, d_C, d_resid, M, N, K, st) : VG_ERR_ARG;
     }
     return VG_ERR_ARG;
+}
+
+/* The kernel vg_gemm would launch for these arguments under the current VG_GEMM_W4 / VG_GEMM_F32_MFMA (read per call, as vg_gemm
+ * does): gemm_family's answer.  0 k_gemm_f16, 1 k_gemm_f16_pp64, 2 k_gemm_f16_w4, 3 k_gemm_f32, 4 k_gemm_f32_mfma, negative: refused.
+ * No launch, no device. */
+int vg_gemm_family(int dtype, int epi, int M, int N, int K) {
+    if (epi < 0 || epi > 4 || (epi == 4 && dtype != 1)) return GF_REFUSED;
+    vg_vit v;                                      // (the switches as vg_gemm's temporary handle reads them)
+    return gemm_family(dtype, epi, M, N, K, v.gemm_w4, v.f32_mfma, gemm_tile256(dtype, N, K));
 }
 
 /* The folded-LayerNorm epilogues of the projection GEMM, alone (test entry point; header: vilgod_hip.h).  Reuses the tower's own
