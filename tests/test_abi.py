@@ -78,3 +78,40 @@ def test_w4_epilogues_match_the_wait_counts_of_the_assembly_block():
             assert r['stores'] >= st_f, (epi, ln, r)        # the allowance is capped at the counter's 63
         zeros = [i for i, w in enumerate(r['compiler_vmcnt']) if w == 0]
         assert len(zeros) <= 2 and (not zeros or zeros[-1] == len(r['compiler_vmcnt']) - 1), (epi, ln, r['compiler_vmcnt'])
+
+
+def _vit_product_text():
+    """{file: text without comments} of csrc/vit.hip and the includes of csrc/ it pulls in, the development build's (csrc/dev/, the
+    build's object directories) left out"""
+    csrc = os.path.join(ROOT, 'vilgod_amd', 'csrc')
+    texts, todo = {}, ['vit.hip']
+    while todo:
+        name = todo.pop()
+        if name in texts or name.startswith('dev/') or not os.path.exists(os.path.join(csrc, name)):
+            continue
+        src = open(os.path.join(csrc, name)).read()
+        todo += re.findall(r'^#include "([^"]+)"', src, flags=re.M)
+        texts[name] = re.sub(r'//[^\n]*|/\*.*?\*/', lambda m: re.sub(r'[^\n]', ' ', m.group(0)), src, flags=re.S)
+    return texts
+
+
+def test_vit_reads_the_environment_in_one_place():
+    """The product text of the ViT translation unit calls getenv only inside VitSwitches::from_env and the two env_* helpers it uses:
+    a handle reads its switches once (vg_vit_create), the handle-less entry points once per call."""
+    texts = _vit_product_text()
+    assert {'vit.hip', 'vit_gemm_kernels.inc', 'vit_gemm_launch.inc', 'vit_attention.inc', 'gemm_w4_loop.inc'} <= set(texts), sorted(texts)
+    stray = []
+    for name, src in texts.items():
+        allowed = []
+        for m in re.finditer(r'static VitSwitches from_env\(\) \{|^static (?:int env_int|bool env_on)\([^\n]*\{', src, flags=re.M):
+            depth, i = 1, m.end()
+            while depth:
+                depth += {'{': 1, '}': -1}.get(src[i], 0)
+                i += 1
+            allowed.append((m.start(), i))
+        for m in re.finditer(r'\bgetenv\b', src):
+            if not any(a <= m.start() < b for a, b in allowed):
+                stray.append((name, src.count('\n', 0, m.start()) + 1))
+    assert not stray, stray
+    helpers = [n for n in texts if 'static VitSwitches from_env()' in texts[n]]
+    assert helpers == ['vit.hip'], helpers

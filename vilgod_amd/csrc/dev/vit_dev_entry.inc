@@ -1,4 +1,17 @@
-// Development build only (-DVG_DEV, libvilgod_hip_dev.so): included by ../vit.hip in place.  development aids (tools/dev/vilgod_hip_dev.h): ablations, cycle-stamp traces
+// Development build only (-DVG_DEV, libvilgod_hip_dev.so): included by ../vit.hip in place.  vg_vit_create's hook and the development
+// aids of tools/dev/vilgod_hip_dev.h: ablations, cycle-stamp traces.
+
+// called by vg_vit_create once the tower's switches are resolved
+static void dev_vit_create(vg_vit* v) {
+    const bool v4 = getenv("VG_GEMM_V4") != nullptr;
+    if (v4) v->resid_h = v->ln_fold = false;      // (k_gemm_f16 has neither epilogue)
+    // k_gemm_f16_x2 serves K % 256 == 0 and merges at most X2_LN_MAXP partial statistics per row: a tower uses it for all of its
+    // projection GEMMs or for none (the two kernels keep the folded LayerNorm's partials at different granularity)
+    v->gemm.gemm_x2 = env_on("VG_GEMM_X2", false) && v->dtype == 1 && v->width % 256 == 0 && v->width / 64 <= X2_LN_MAXP && !v->resid_h && !v4;
+}
+
+extern "C" {
+
 /* ablation variants of the f16 GEMMs (development aid, epi 0 only): k_gemm_f16 var 0 = as shipped, 1 = no DMA inside the
  * K loop, 2 = DMA only (no LDS reads / MFMA), 3 = no epilogue; k_gemm_f16_pp var 22 = as shipped (4 stages, one phase per
  * K-step), 20 = two phases per K-step, 21 / 23 = 5 stages */
@@ -10,7 +23,7 @@ int vg_gemm_variant(int var, const void* d_X, const void* d_Wt, const float* d_b
     case V:                                                                                                                \
         (void)hipFuncSetAttribute((const void*)k_gemm_f16<EPI_BIAS, V>, hipFuncAttributeMaxDynamicSharedMemorySize, G_LDS_BYTES); \
         hipLaunchKernelGGL((k_gemm_f16<EPI_BIAS, V>), dim3(nwg), dim3(512), G_LDS_BYTES, st, (const f16*)d_X, (const f16*)d_Wt, \
-                           d_bias, d_C, nullptr, M, N, K, ldc, gemm_chunk_tiles(N, K));                                   \
+                           d_bias, d_C, nullptr, M, N, K, ldc, gemm_tile_chunk(GF_F16, N, K));                            \
         break;
     switch (var) { VG_VAR(0) VG_VAR(1) VG_VAR(2) VG_VAR(3)
         case 20: return launch_gemm_pp<EPI_BIAS, 4, false>(d_X, d_Wt, d_bias, d_C, nullptr, M, N, K, ldc, st, nullptr);
@@ -65,3 +78,4 @@ int vg_attention_trace(const void* d_qkv, void* d_out, int n_crops, int T, int W
     return launch_attention<false>((const f16*)d_qkv, (f16*)d_out, T, W, heads, ld, items, nullptr, st);
 }
 
+}  // extern "C"

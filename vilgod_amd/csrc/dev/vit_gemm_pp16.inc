@@ -1,4 +1,4 @@
-// Development build only (-DVG_DEV, libvilgod_hip_dev.so): included by ../vit.hip in place.  K-step-32 predecessor of k_gemm_f16_pp64 (tools/dev only)
+// Development build only (-DVG_DEV, libvilgod_hip_dev.so): included by vit_dev_launchers.inc in place.  K-step-32 predecessor of k_gemm_f16_pp64 (tools/dev only)
 // ---------------------------------------------------------------------------------------------
 // The same ping-pong schedule on v_mfma_f32_16x16x32_f16 (one MFMA spans the whole 32-wide K-step of a 16 x 16 block:
 // 32 MFMAs of 16 cycles per wave and K-step instead of 16 of 32).  MI355X_MICROARCH.md "DVFS give-back" item 7: on

@@ -1,4 +1,4 @@
-// Development build only (-DVG_DEV, libvilgod_hip_dev.so): included by ../vit.hip in place.  superseded K-step-32 ping-pong kernel: kept for the cycle-stamp tools (tools/dev), not in the product library
+// Development build only (-DVG_DEV, libvilgod_hip_dev.so): included by vit_dev_launchers.inc in place.  superseded K-step-32 ping-pong kernel: kept for the cycle-stamp tools (tools/dev), not in the product library
 // ---------------------------------------------------------------------------------------------
 // Ping-pong GEMM: 256 x 256 x 32 tiles, 8 waves = two groups of four (group = 128-row half of the tile, one wave of each
 // group per SIMD), each wave 128 (m) x 64 (n).  A PHASE is one k16 sub-step of one wave: LOAD segment (6 ds_read_b128 for

@@ -1,4 +1,4 @@
-// Development build only (-DVG_DEV, libvilgod_hip_dev.so): included by ../vit.hip in place.  measured slower than k_gemm_f16_pp64 on every projection shape (LAB_NOTES.md section 3, round 3): development build only (VG_GEMM_X2=1)
+// Development build only (-DVG_DEV, libvilgod_hip_dev.so): included by vit_dev_launchers.inc in place.  measured slower than k_gemm_f16_pp64 on every projection shape (LAB_NOTES.md section 3, round 3): development build only (VG_GEMM_X2=1)
 // ---------------------------------------------------------------------------------------------
 // k_gemm_f16_x2: TWO independent 4-wave workgroups per CU, each a 128 x 256 tile (one "group" of k_gemm_f16_pp64).
 // Why: in k_gemm_f16_pp64 the one workgroup that owns a CU reaches its epilogue with all eight waves at once, and the matrix pipe
@@ -300,9 +300,7 @@ static int launch_gemm_x2(const void* X, const void* Wt, const float* bias, void
     if (M % 128 || N % 256 || K % 256) return VG_ERR_ARG;
     if (LN == 1 && (K / 64 > X2_LN_MAXP || !ln_c1 || !ln_stats)) return VG_ERR_ARG;
     if (LN == 2 && (ldc != N || !ln_stats || !ln_x16)) return VG_ERR_ARG;
-    const int ntn = N / 256;
-    int cwt = gemm_chunk_tiles_256(ntn);
-    if (getenv("VG_GEMM_CW")) { cwt = atoi(getenv("VG_GEMM_CW")); if (cwt < 1 || ntn % cwt) cwt = ntn; }      // tile-order sweep
+    const int ntn = N / 256, cwt = gemm_tile_chunk(GF_PP64, N, K);      // (k_gemm_f16_pp64's tile order and its sweep)
     hipLaunchKernelGGL((k_gemm_f16_x2<EPI, LN, TRACE>), dim3((M / 128) * ntn), dim3(256), 0, st, (const f16*)X, (const f16*)Wt, bias, C, resid,
                        M, N, K, ldc, cwt, ln_c1, ln_stats, ln_x16, trace);
     VG_LAUNCH_CHECK();
