@@ -88,6 +88,26 @@ typedef struct vg_render_params {
 int vg_render_crops_ex(const float* d_origin, const int32_t* d_seg_off, int n_clusters, const float* d_view_rot, int n_views,
                        const float* d_lut, const vg_render_params* params, void* d_out, int out_kind, void* stream);
 
+/* The crops at a `classification.image_size` other than 224 (tools/configs/preprocessing.yaml:91).  The reference interpolates
+ * get_img()'s image to image_size^2 (bilinear, align_corners=True), permutes, truncates to uint8 and builds a PIL image
+ * (src/vilgod/zero_shot_detector.py:405-410); CLIP's preprocess then opens with Resize(224, BICUBIC) (third_party/CLIP/clip/clip.py:79-86),
+ * Pillow's antialiased 8-bit resample (src/libImaging/Resample.c: horizontal, then vertical pass, clip8((2^21 + sum pixel * k) >> 22)).
+ * At 224 that resize is the identity and vg_render_crops[_ex] write the crops themselves; this entry point computes the chain for
+ * 65 <= image_size <= 448, bit for bit (below 65 torch's CPU interpolate sums in another order: DESIGN.md section 4).
+ *   in_kind 0: d_in = float [n, in_side, in_side], vg_render_crops[_ex] out_kind 3 (in_side = resolution - 2: 14 .. 126): the whole chain
+ *   in_kind 1: d_in = uint8 [n, image_size, image_size], single-channel images at image_size already: the resample alone (in_side unused)
+ *   d_bounds [224,2] = (first input pixel, tap count) and d_coef [224,ksize] = the taps in 2^-22 units per output pixel: Pillow's
+ *   precompute_coeffs + normalize_coeffs_8bpc for image_size -> 224 (vilgod_amd/pil_resample.py; one table serves both passes).
+ *   ksize >= ceil(2 * max(image_size / 224, 1)) * 2 + 1, the taps Pillow reserves (5 .. 9).
+ *   d_lut as vg_render_crops; out_kind 0, 1, 2, 4, 5 with the layouts and value mappings documented there (d_out sized for n crops).
+ * One workgroup per crop; no allocation, no synchronisation.  n <= 0: VG_OK.  VG_ERR_ARG (nothing launched, outputs untouched) for an
+ * image_size outside 65 .. 448, null pointers, other kinds, an in_side outside 14 .. 126 for in_kind 0, a ksize below the bound above. */
+#define VG_PREPROCESS_MIN_IMAGE_SIZE 65
+#define VG_PREPROCESS_MAX_IMAGE_SIZE 448
+int vg_clip_preprocess(const void* d_in, int in_kind, int n, int in_side, int image_size,
+                       const int32_t* d_bounds /*[224,2]*/, const int32_t* d_coef /*[224,ksize]*/, int ksize,
+                       const float* d_lut, void* d_out, int out_kind, void* stream);
+
 /* ---- CLIP ViT image tower + zero-shot scores (rows D7, D9) --------------------------------------
  * Replaces ClipWrapper.predict_clip_labels' GPU part, src/utils/clip_utils.py:37-44:
  *   model.encode_image (third_party/CLIP/clip/model.py:340-341 -> VisionTransformer.forward :223-240,

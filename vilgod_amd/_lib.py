@@ -119,6 +119,7 @@ class RenderParams(ctypes.Structure):
 
 RENDER_RESOLUTION = (_DEFINES['RENDER_MIN_RESOLUTION'], _DEFINES['RENDER_MAX_RESOLUTION'])
 RENDER_DEPTH = (_DEFINES['RENDER_MIN_DEPTH'], _DEFINES['RENDER_MAX_DEPTH'])
+PREPROCESS_IMAGE_SIZE = (_DEFINES['PREPROCESS_MIN_IMAGE_SIZE'], _DEFINES['PREPROCESS_MAX_IMAGE_SIZE'])     # vg_clip_preprocess
 
 
 def ptr(t):

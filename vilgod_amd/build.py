@@ -27,6 +27,7 @@ COMMON = ['-O3', '-fPIC', '-std=c++17', f'--offload-arch={ARCH}', f'-I{INCLUDE}'
 SOURCES = {
     'api.hip': [],
     'render.hip': ['-ffp-contract=off'],
+    'preprocess.hip': ['-ffp-contract=off'],
     'ground.hip': ['-ffp-contract=off'],
     'cluster.hip': ['-ffp-contract=off'],
     'hdbscan_tree.cpp': ['-ffp-contract=off'],

@@ -30,7 +30,7 @@ from .frame_state import (FrameState, pack_clusters, vote, static_from_entropy, 
                           sublist_offsets, PACK_MAX_LABEL_BOUND)
 from . import patchworkpp as gpw
 from .hdbscan import HDBSCAN
-from .projection import RealisticProjection, VIEWS_4, VIEWS_6
+from .projection import RealisticProjection, VIEWS_4, VIEWS_6, check_image_size
 from .clip_wrapper import ClipWrapper
 
 # tools/configs/preprocessor/waymo.yaml:104-140
@@ -105,7 +105,7 @@ class PseudoLabelPipeline:
     def __init__(self, preprocessor_cfg=None, device='cuda:0', vit_dtype='f16', n_views=4, max_points=300_000,
                  clip_model_path='../models/clip/', min_range=1.5, z_offset=1.723, plane_seed=666, clip=None,
                  box_mode='reference', box_workers=4, vit_graph=False, angle_mode='reference', cu_reserve=None, cu_tower=None,
-                 hierarchy=None, pack='host'):
+                 hierarchy=None, pack='host', image_size=224):
         cfg = preprocessor_cfg if preprocessor_cfg is not None else default_preprocessor_cfg()
         self.cfg = cfg
         self.device = torch.device(device)
@@ -143,6 +143,9 @@ class PseudoLabelPipeline:
         clip_cfg = _get(cfg, 'clip')
         self.clip = clip if clip is not None else ClipWrapper(clip_cfg, clip_model_path, device=self.device, dtype=vit_dtype)
         self.vit_dtype = vit_dtype
+        # `classification.image_size` (zero_shot_detector.py:405-410): 224 = the renderer's own crops; 65 .. 448 go through
+        # vg_clip_preprocess (projection.render_frame), others are refused here
+        self.image_size = check_image_size(image_size)
         self._init_classes(clip_cfg)
         self.class_names = list(_get(cfg, 'class_names', ['Vehicle', 'Pedestrian', 'Cyclist']))
         self.plane_seed = int(plane_seed)
@@ -598,8 +601,9 @@ class PseudoLabelPipeline:
             h_verdict[c, kv] = bool(P.active[kv]) and volume >= P.min_volume and (not P.has_max_volume or volume <= P.max_volume)
 
     # [D1]-[D9]
-    def classify(self, d_X, d_index, d_seg, transform_to_ego):
+    def classify(self, d_X, d_index, d_seg, transform_to_ego, image_size=None):
         n = (d_seg.numel() - 1) * self.projection.num_views
+        size = self.image_size if image_size is None else image_size      # (a stage's own `image_size` argument overrides the pipeline's)
         enc = self.clip.encoder
         if self.vit_dtype == 'f16' and enc.cfg['patch'] == 16 and enc.cfg['resolution'] == 224:
             # the renderer writes the patch-embedding GEMM's A operand directly (no CHW crops, no im2col pass)
@@ -613,14 +617,14 @@ class PseudoLabelPipeline:
                 if self._graph_cls is None:
                     self._graph_cls = GraphClassifier(enc, self.clip.text_features, max_crops=max(512, n), patch_width=256 if self.patch_1ch else 768)
                 g = self._graph_cls
-                self.projection.render_frame(d_X, d_index, d_seg, transform_to_ego, out=pmode, out_buf=g.patch_buffer(n))
+                self.projection.render_frame(d_X, d_index, d_seg, transform_to_ego, out=pmode, out_buf=g.patch_buffer(n), image_size=size)
                 with self._vit_in_turn():
                     probs, top1, score = g.classify(n, self.clip.text_features)
                 return probs.clone(), top1.clone(), score.clone()
-            patches = self.projection.render_frame(d_X, d_index, d_seg, transform_to_ego, out=pmode)
+            patches = self.projection.render_frame(d_X, d_index, d_seg, transform_to_ego, out=pmode, image_size=size)
             self._mark('render')
             return self._on_vit_stream(lambda: clip_scores(enc.encode_patches(patches, n), self.clip.text_features), patches, n)
-        crops = self.projection.render_frame(d_X, d_index, d_seg, transform_to_ego, out='f16' if self.vit_dtype == 'f16' else 'f32')
+        crops = self.projection.render_frame(d_X, d_index, d_seg, transform_to_ego, out='f16' if self.vit_dtype == 'f16' else 'f32', image_size=size)
         if enc.cfg['patch'] == 16:
             return self.clip.predict_probs(crops)
         # other towers (ViT-B/32, ViT-L/14: CHW crops, im2col in the tower) take the patch-16 path's CU-masked stream and frames-in-flight turn

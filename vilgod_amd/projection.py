@@ -13,7 +13,7 @@ import numpy as np
 import torch
 from scipy.spatial.transform import Rotation
 
-from . import _lib
+from . import _lib, pil_resample
 from ._lib import lib, ptr, stream_ptr, check
 
 CLIP_MEAN = (0.48145466, 0.4578275, 0.40821073)   # third_party/CLIP/clip/clip.py:85
@@ -47,6 +47,15 @@ def _gaussian_taps(sigma):
     k2 = k2 / k2.sum()
     k2 = torch.Tensor((k2[None] * np.ones((1, 1, 1), np.float32)) / torch.sum(k2[None]))[0]
     return float(k2[0, 0]), float(k2[0, 1]), float(k2[1, 1])
+
+
+def check_image_size(image_size):
+    """`classification.image_size` as csrc/preprocess.hip computes it: an integer 65 .. 448 (224: the renderer's own crops).  Below 65
+    torch's CPU interpolate, which the reference runs, sums in another order than the kernel; above 448 the tap tables outgrow it."""
+    lo, hi = _lib.PREPROCESS_IMAGE_SIZE
+    if isinstance(image_size, bool) or not isinstance(image_size, (int, np.integer)) or not lo <= image_size <= hi:
+        raise NotImplementedError(f'image_size = {image_size!r}: csrc/preprocess.hip resizes to integers {lo} .. {hi}')
+    return int(image_size)
 
 
 def _as_tuple(v):
@@ -124,14 +133,18 @@ class RealisticProjection:
         self._d_rot = self.rot_mat.reshape(-1, 9).to(self.device)
         self._d_lut = lut.to(self.device)
         self._d_timg = torch.from_numpy(np.ascontiguousarray(t_img)).to(self.device)
+        self._pil_tables = {}                    # image_size -> (bounds, coef, ksize) on the device (_resample_tables)
 
     # -- frame-level fused path -----------------------------------------------------------------
-    def render_frame(self, points, index, seg_off, transform_to_ego, out='f16', stream=None, out_buf=None):
+    def render_frame(self, points, index, seg_off, transform_to_ego, out='f16', stream=None, out_buf=None, image_size=224):
         """points: [N,>=3] float32 CUDA tensor (ref frame, `points_ref_wo_ground`);
         index: [Ptot] int32 packed cluster point indices (cluster after cluster) or None;
         seg_off: [C+1] int32 CUDA; transform_to_ego: 4x4 float64 (numpy or tensor).
-        Returns crops for all C*V (cluster-major, like torch.cat of get_img results)."""
+        Returns crops for all C*V (cluster-major, like torch.cat of get_img results).
+        image_size: `classification.image_size` (zero_shot_detector.py:405-410).  224: the renderer writes the crops itself; 65 .. 448:
+        it writes its raw images and vg_clip_preprocess resizes them as the reference and PIL do (csrc/preprocess.hip)."""
         kind = {'u8': OUT_U8, 'f32': OUT_F32, 'f16': OUT_F16, 'raw110': OUT_RAW110, 'patch16': OUT_PATCH16, 'patch16c1': OUT_PATCH16_1CH}[out]
+        image_size = check_image_size(image_size)
         dev = points.device
         n_clusters = seg_off.numel() - 1
         ptot = int(index.numel()) if index is not None else int(points.shape[0])
@@ -180,9 +193,24 @@ class RealisticProjection:
         origin = torch.empty((ptot, 3), dtype=torch.float32, device=dev)
         check(lib.vg_to_origin(ptr(ego), ptr(pt_cluster), ptot, ptr(med), ptr(rot), ptr(self._d_timg), ptr(origin), sp),
               'vg_to_origin')
-        self._render(origin, seg_off, n_clusters, result, kind, sp)
+        if image_size == 224 or kind == OUT_RAW110:
+            self._render(origin, seg_off, n_clusters, result, kind, sp)
+        else:
+            raw = torch.empty((n, self.image_side, self.image_side), dtype=torch.float32, device=dev)
+            self._render(origin, seg_off, n_clusters, raw, OUT_RAW110, sp)
+            bounds, coef, ksize = self._resample_tables(image_size, dev)
+            check(lib.vg_clip_preprocess(ptr(raw), 0, n, self.image_side, image_size, ptr(bounds), ptr(coef), ksize, ptr(self._d_lut),
+                                         ptr(result), kind, sp), 'vg_clip_preprocess')
         self._last = dict(ego=ego, median=med, origin=origin, rot=rot)
         return result
+
+    def _resample_tables(self, image_size, dev):
+        """PIL's bicubic tables for image_size -> 224 on the device, computed once per size (pil_resample.py)"""
+        cache = self._pil_tables
+        if image_size not in cache:
+            bounds, coef, ksize = pil_resample.bicubic_coeffs(image_size, 224)
+            cache[image_size] = (torch.from_numpy(bounds).to(dev), torch.from_numpy(coef).to(dev), ksize)
+        return cache[image_size]
 
     def render_origin(self, origin, seg_off, out='f16', stream=None):
         """Render from already origin-transformed points (D1 output), [Ptot,3] float32 CUDA."""

@@ -8,7 +8,7 @@ Stage names, keyword arguments, skip-if-already-done rules and the two pickle fa
   calculate_entropy_scores(n_neighbouring_frames, skip_frames, ...) :153-195
   spatial_clustering(force, n_frames)            (n_frames >= 1)    :197-259
   filter_detections(force)                                          :261-297
-  classification(image_size, key, aggregation, valid_only, ...)     :329-420
+  classification(image_size, key, aggregation, valid_only, ...)     :329-420 (image_size 65 .. 448, voting)
   fit_bounding_boxes_simple(method, force, valid_only, ...)         :422-462 (static branch)
   evaluate_sequence(modes, classification_key, ...)                 :826-857
   sync_lidar_frames(mode)                                           :105-123
@@ -34,6 +34,7 @@ import numpy as np
 import torch
 
 from . import dist as vdist
+from ._lib import PREPROCESS_IMAGE_SIZE
 from .boxes import box_method
 from .frame_state import FrameState, select_rows_device, sublist_offsets
 from .pipeline import PseudoLabelPipeline
@@ -693,11 +694,16 @@ class ZeroShotDetector:
         self.sync_lidar_frames()
 
     def _classification_context(self, image_size=224, aggregation='voting', **kwargs):
-        if image_size != 224 or aggregation != 'voting':
-            raise NotImplementedError('image_size 224 and voting aggregation (preprocessing.yaml) only')
+        # image_size (zero_shot_detector.py:405-410): 224 is the renderer's own output, the other sizes of the range go through
+        # csrc/preprocess.hip (bilinear to image_size, uint8, PIL's bicubic back to 224); the reference's `mean` aggregation is not built
+        lo, hi = PREPROCESS_IMAGE_SIZE
+        if isinstance(image_size, bool) or not isinstance(image_size, (int, np.integer)) or not lo <= image_size <= hi \
+                or aggregation != 'voting':
+            raise NotImplementedError(f'image_size: integers {lo} .. {hi} and voting aggregation only '
+                                      f'(got image_size={image_size!r}, aggregation={aggregation!r})')
         p = self.pipe
         active = list(self.cfg.pipeline_active)
-        return {'key': kwargs.get('key', 'clip'), 'valid_only': kwargs.get('valid_only', False),
+        return {'key': kwargs.get('key', 'clip'), 'valid_only': kwargs.get('valid_only', False), 'image_size': int(image_size),
                 # the static rectangles of the same clusters (box_mode='reference': a helper process per request) are computed while
                 # the GPU encodes the crops; fit_bounding_boxes_simple collects them (they do not depend on the classes)
                 # -- min-area rectangles only: the request carries no method, and an L-shape fit runs on the GPU in the box stage
@@ -728,7 +734,7 @@ class ZeroShotDetector:
         d_index, d_seg = self._cluster_lists(fnr, rows)
         if ctx['prefetch_boxes']:
             self._box_prefetch[fnr] = ([int(r) for r in rows], self._fit_rows(fnr, rows, X, wait=False))
-        probs, top1, score = pw.classify(X, d_index, d_seg, fs.transform_to_ego)
+        probs, top1, score = pw.classify(X, d_index, d_seg, fs.transform_to_ego, image_size=ctx['image_size'])
         self._scores[fnr] = probs
         pw.vote_classes(fs, ctx['key'], which, top1.cpu().numpy(), score.cpu().numpy())
 
