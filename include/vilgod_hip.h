@@ -213,6 +213,33 @@ int vg_attention(const void* d_qkv, void* d_out, int n_crops, int T, int W, int 
  * Anything else (T outside 1 .. 1024, heads * 64 != W, null pointers) is VG_ERR_ARG and nothing is launched. */
 int vg_attention_rows(int dtype, const void* d_qkv, void* d_out, int n_crops, int T, int W, int heads, int ld, int q_tiles, void* stream);
 
+/* The causal attention of the text tower alone (third_party/CLIP/clip/model.py:320-326 build_attention_mask, applied at :186): row q of
+ * an item sees keys 0 .. q.  vg_attention_rows' layouts, handle-less, every query row computed.
+ * dtype 1: k_attention_f16 with its CAUSAL parameter (key blocks above a wave's query tile skipped, the diagonal block masked), T <= 224,
+ *   ld >= 3 W, ld % 8 == 0.   dtype 0: k_attention_f32<CAUSAL>, ld == 3 W, T <= 282 (its LDS bound).
+ * Row i equals, bit for bit, row i of vg_attention_rows on the item's first i + 1 tokens.
+ * Anything else (a longer T, heads * 64 != W, null pointers) is VG_ERR_ARG and nothing is launched. */
+int vg_attention_causal_rows(int dtype, const void* d_qkv, void* d_out, int n_items_crops, int T, int W, int heads, int ld, void* stream);
+
+/* ---- CLIP text tower: replaces model.encode_text (third_party/CLIP/clip/model.py:343-356) as ClipWrapper.__init__ calls it for the
+ * class prompts (src/utils/clip_utils.py:22-26).  The image tower's blocks (VitRun) with causal attention, a token-table front end
+ * and a head that reads one row per prompt.  dtype as vg_vit_create; the stream stays fp32 (no class-row last block). */
+typedef struct vg_text vg_text;
+/* Constraints: width % 128 == 0, width <= 1024, heads * 64 == width (vg_vit_create's), 1 <= ctx <= 224, vocab >= 1 (model.py:288-300). */
+int vg_text_create(vg_text** out, int width, int layers, int heads, int ctx, int vocab, int out_dim, int dtype);
+void vg_text_destroy(vg_text* t);
+/* one tensor by its reference state_dict name (model.py:288-300: token_embedding.weight [vocab, width], positional_embedding
+ * [ctx, width], transformer.resblocks.N.* (model.py:171-183), ln_final.weight / .bias, text_projection [width, out_dim]); h_data: HOST
+ * float32.  A table whose size does not match the handle's is VG_ERR_ARG.  Synchronous. */
+int vg_text_set_weight(vg_text* t, const char* name, const float* h_data, int64_t numel);
+/* bytes of device workspace for n_prompts; the caller zero-fills it once. */
+int64_t vg_text_workspace_bytes(const vg_text* t, int n_prompts);
+/* d_tokens: int32 [n, ctx] (clip.py:197-237 tokenize); d_eot: int32 [n], the position whose row the head reads -- the first maximum of
+ * the prompt's ids (model.py:354 argmax), computed by the caller; d_feat: float32 [n, out_dim] = ln_final(x[p, eot[p]]) @
+ * text_projection, NOT normalised (model.py:352-354).  A token id outside [0, vocab) or an eot outside [0, ctx) is clamped on the
+ * device: a wrong row, never a read outside the tables.  The first encode of a handle allocates (folded LayerNorms) like vg_vit_encode's. */
+int vg_text_encode(vg_text* t, const int32_t* d_tokens, const int32_t* d_eot, int n_prompts, void* d_workspace, float* d_feat, void* stream);
+
 /* ---- captured classification: the hipGraph loop of BASELINE config 5 ------------------------------------------------
  * vg_vit_encode + vg_clip_scores of one frame (the reference's per-chunk model.encode_image + softmax, clip_utils.py:37-61) as ONE
  * hipGraph per distinct crop count: captured on the first frame that has that many crops, replayed for every later one

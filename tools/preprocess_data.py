@@ -94,7 +94,8 @@ def main(argv=None):
                                    box_mode=dev.get('box_mode', 'reference'), box_workers=dev.get('box_workers', 4),
                                    angle_mode=dev.get('angle_mode', 'reference'), vit_graph=bool(dev.get('vit_graph', False)),
                                    cu_reserve=int(dev.get('cu_reserve', 0)), cu_tower=dev.get('cu_tower', 'complement'),
-                                   pack=dev.get('pack', 'host'))
+                                   pack=dev.get('pack', 'host'), text=dev.get('text', 'host'),
+                                   text_dtype=dev.get('text_dtype', 'f32'))
     logger.info(f'CLIP weights: {pipeline.clip.weights_source}')
     from vilgod_amd import clip_weights
     tc = pipeline.clip.encoder.cfg

@@ -1,5 +1,6 @@
 """Text side of `ClipWrapper.__init__`: the 24 prompts -> L2-normalised text features, computed ONCE at
-start-up with plain torch (not a kernel, not on the hot path) and cached next to the checkpoint.
+start-up with plain torch (not a kernel, not on the hot path) and cached next to the checkpoint -- or, with tower='device' /
+`TextTower`, by the text tower of the C ABI on the GPU (vg_text_*, csrc/vit_text.inc), which long class lists want.
 
 Mirrors
   clip.tokenize                     third_party/CLIP/clip/clip.py:197-237        (sot + BPE + eot, zero padded to 77)
@@ -151,13 +152,102 @@ def encode_text(sd, tokens, device='cpu'):
     return (x[torch.arange(n, device=device), eot] @ sd['text_projection']).float().cpu()
 
 
-def text_features(ckpt_path, prompts, bpe_path=None, device='cpu'):
-    """clip_utils.py:22-26: normalised features of the prompts (float32 [n, embed]; the reference computes them in the
-    model's dtype -- fp16 on a GPU -- so its values differ from these in the 3rd-4th digit)."""
+def text_config(sd):
+    """The text tower's sizes, read from its tensors (model.py:288-300)."""
+    vocab, width = sd['token_embedding.weight'].shape
+    layers = len([k for k in sd if k.startswith('transformer.resblocks.') and k.endswith('attn.in_proj_weight')])
+    return {'width': int(width), 'layers': layers, 'heads': max(int(width) // 64, 1), 'ctx': int(sd['positional_embedding'].shape[0]),
+            'vocab': int(vocab), 'output_dim': int(sd['text_projection'].shape[1])}
+
+
+class TextTower:
+    """CLIP.encode_text (model.py:343-356) on the device: owns a vg_text handle (include/vilgod_hip.h) and one workspace sized for a
+    chunk of prompts.  dtype 'f32' is the parity mode, 'f16' the fp16 tower on the fp32 stream."""
+
+    CHUNK = 256          # prompts per vg_text_encode: 256 x 77 rows are exactly 77 row tiles of the projection GEMMs
+
+    def __init__(self, state_dict, dtype='f32', device='cuda'):
+        import ctypes
+        from ._lib import lib, check
+        keep = ('token_embedding.', 'positional_embedding', 'transformer.', 'ln_final.', 'text_projection')
+        sd = {k: v for k, v in state_dict.items() if k.startswith(keep)}
+        self.cfg = text_config(sd)
+        self.dtype = dtype
+        self.device = torch.device(device)
+        self._h = None
+        h = ctypes.c_void_p()
+        c = self.cfg
+        check(lib.vg_text_create(ctypes.byref(h), c['width'], c['layers'], c['heads'], c['ctx'], c['vocab'], c['output_dim'],
+                                 {'f32': 0, 'f16': 1}[dtype]), 'vg_text_create')
+        self._h = h
+        with torch.cuda.device(self.device):
+            for name, t in sd.items():
+                t = t.detach().to(torch.float32).contiguous().cpu()
+                check(lib.vg_text_set_weight(self._h, name.encode(), ctypes.c_void_p(t.data_ptr()), t.numel()), f'vg_text_set_weight({name})')
+        self._ws = None
+        self._ws_prompts = 0
+
+    def close(self):
+        """Destroys the handle (the token table alone is 100 to 150 MB) and drops the workspace."""
+        from ._lib import lib
+        h, self._h = getattr(self, '_h', None), None
+        if h is not None and lib is not None:
+            lib.vg_text_destroy(h)
+        self._ws = None
+
+    __del__ = close
+
+    def _workspace(self, n):
+        from ._lib import lib
+        if self._ws is None or n > self._ws_prompts:
+            self._ws = None
+            self._ws = torch.zeros(int(lib.vg_text_workspace_bytes(self._h, n)), dtype=torch.uint8, device=self.device)
+            self._ws_prompts = n
+        return self._ws
+
+    def encode_chunk(self, tokens, eot, stream=None):
+        """One vg_text_encode: tokens int32 [n, ctx] and eot int32 [n] on the device -> float32 [n, embed]."""
+        from ._lib import lib, ptr, stream_ptr, check
+        n = tokens.shape[0]
+        feat = torch.empty((n, self.cfg['output_dim']), dtype=torch.float32, device=self.device)
+        if n:
+            with torch.cuda.device(self.device):
+                check(lib.vg_text_encode(self._h, ptr(tokens), ptr(eot), n, ptr(self._workspace(n)), ptr(feat), stream_ptr(stream)), 'vg_text_encode')
+        return feat
+
+    def encode(self, tokens, stream=None):
+        """tokens: integer [n, ctx] (numpy or torch) -> float32 [n, embed] on the device, NOT normalised, in chunks of CHUNK prompts."""
+        tok = torch.as_tensor(np.asarray(tokens.cpu() if torch.is_tensor(tokens) else tokens)).long()
+        assert tok.ndim == 2 and tok.shape[1] == self.cfg['ctx'], (tuple(tok.shape), self.cfg['ctx'])
+        eot = tok.argmax(dim=-1).to(torch.int32).to(self.device)           # the first maximum: torch's argmax, as model.py:354
+        tok = tok.to(torch.int32).to(self.device).contiguous()
+        if tok.shape[0] > self.CHUNK:
+            self._workspace(self.CHUNK)
+        out = [self.encode_chunk(tok[i:i + self.CHUNK], eot[i:i + self.CHUNK], stream) for i in range(0, tok.shape[0], self.CHUNK)]
+        return torch.cat(out) if out else torch.empty((0, self.cfg['output_dim']), dtype=torch.float32, device=self.device)
+
+
+def tokenize_prompts(prompts, bpe_path=None):
     vocab = find_bpe_vocab(bpe_path)
     if vocab is None:
         raise FileNotFoundError('bpe_simple_vocab_16e6.txt.gz not found: put third_party/CLIP on PYTHONPATH (README.md:130-133 '
                                 'of the reference) or pass its path (paths.clip_bpe)')
-    tok = tokenize(BpeTokenizer(vocab), list(prompts))
-    f = encode_text(load_text_state_dict(ckpt_path), tok, device=device)
+    return tokenize(BpeTokenizer(vocab), list(prompts))
+
+
+def text_features(ckpt_path, prompts, bpe_path=None, device='cpu', tower='host'):
+    """clip_utils.py:22-26: normalised features of the prompts (float32 [n, embed]; the reference computes them in the
+    model's dtype -- fp16 on a GPU -- so its values differ from these in the 3rd-4th digit).  tower='device': the same tokens through
+    fp32 TextTower on `device` (a CUDA device; 'cpu' means the current one) instead of the host's torch."""
+    if tower not in ('host', 'device'):
+        raise ValueError(f"tower must be 'host' or 'device', not {tower!r}")
+    tok = tokenize_prompts(prompts, bpe_path)
+    if tower == 'device':
+        t = TextTower(load_text_state_dict(ckpt_path), dtype='f32', device='cuda' if str(device) == 'cpu' else device)
+        try:
+            f = t.encode(tok).cpu()
+        finally:
+            t.close()
+    else:
+        f = encode_text(load_text_state_dict(ckpt_path), tok, device=device)
     return (f / f.norm(dim=-1, keepdim=True)).numpy()

@@ -216,8 +216,16 @@ def validate_class_list(class_list, class_mapping=None):
 
 
 class ClipWrapper:
-    def __init__(self, clip_cfg, model_path, device=None, dtype='f16', synthetic_seed=0):
+    def __init__(self, clip_cfg, model_path, device=None, dtype='f16', synthetic_seed=0, text='host', text_dtype='f32'):
+        """text: where a checkpoint's class prompts are encoded at start-up.  'host': plain torch on the CPU, cached next to the
+        checkpoint (`*.text_features.npy`); 'device': clip_text.TextTower on `device` in `text_dtype` ('f32' | 'f16'), no cache file read
+        or written, the text handle destroyed afterwards.  Without a checkpoint both use the seeded synthetic features."""
         assert model_path is not None, 'model_path is None'
+        if text not in ('host', 'device'):
+            raise ValueError(f"text must be 'host' or 'device', not {text!r}")
+        if text_dtype not in DTYPES:
+            raise ValueError(f"text_dtype must be 'f32' or 'f16', not {text_dtype!r}")
+        self.text_mode, self.text_dtype, self._ckpt = text, text_dtype, None
         if device is None:
             device = 'cuda'
         self.device = torch.device(device)
@@ -232,8 +240,13 @@ class ClipWrapper:
         model_name = str(g('model_name', 'ViT-B-16.pt'))
         tower = clip_weights.tower_config(model_name)        # raises for ViT-L-14-336px.pt; None for a name it does not know
         ckpt = os.path.join(str(model_path), model_name)
-        if os.path.exists(ckpt):
+        if os.path.exists(ckpt) and text == 'device':
             weights = clip_weights.load_state_dict(ckpt)
+            self.weights_source = self._ckpt = ckpt
+            text = self.encode_prompts([self.template.format(c) for c in class_list]).cpu()
+        elif os.path.exists(ckpt):
+            weights = clip_weights.load_state_dict(ckpt)
+            self._ckpt = ckpt
             tf_path = ckpt + '.text_features.npy'
             if not os.path.exists(tf_path):
                 # clip_utils.py:22-26: tokenise the prompts, encode_text, normalise -- once, with plain torch, then cached
@@ -256,6 +269,22 @@ class ClipWrapper:
             text = clip_weights.synthetic_text_features(synthetic_seed, len(class_list), weights['proj'].shape[1])
         self.text_features = text.to(self.device).contiguous()
         self.encoder = VitEncoder(weights, dtype=dtype, device=self.device)
+
+    def encode_prompts(self, prompts):
+        """Normalised text features [n, embed] (float32, on the device) of any prompts, for scoring against another list than
+        clip.class_list: the checkpoint's text tower on the GPU (clip_text.TextTower in `text_dtype`), built for the call and destroyed
+        after it -- the token table is 100 to 150 MB and is not kept."""
+        from . import clip_text
+        if self._ckpt is None:
+            raise RuntimeError('encode_prompts needs a checkpoint on disk (the synthetic mode has no text tower)')
+        tok = clip_text.tokenize_prompts(list(prompts), os.environ.get('CLIP_BPE'))
+        tower = clip_text.TextTower(clip_text.load_text_state_dict(self._ckpt), dtype=self.text_dtype, device=self.device)
+        try:
+            f = tower.encode(tok)
+            torch.cuda.synchronize(self.device)
+        finally:
+            tower.close()
+        return f / f.norm(dim=-1, keepdim=True)
 
     def view(self):
         """The same model for another worker stream: shared weights and text features, own ViT workspace."""

@@ -31,12 +31,13 @@
 //     vit_gemm_kernels.inc   the EPI enum, k_gemm_f16, k_gemm_f32, k_gemm_f32_mfma, k_gemm_f16_pp64, k_gemm_f16_w4 (K loop: gemm_w4_loop.inc,
 //                            written by gen_gemm_w4.py), k_splitk_resid
 //     vit_gemm_launch.inc    tile order, splitk_plan, gemm_family (which kernel), launch_gemm_pp64 / _w4 / _resid_tail, launch_gemm (the launch path)
-//     vit_attention.inc      k_attention_f16, k_attention_f16_long, k_attention_f32, launch_attention
+//     vit_attention.inc      k_attention_f16 (plain and causal), k_attention_f16_long, k_attention_f32 (plain and causal), launch_attention[_causal / _f32]
 //     vit_stage_kernels.inc  k_im2col, k_embed_lnpre, k_layernorm, k_head, k_ln_fold, k_conv1_fold, class-row gather / scatter
 //     vit_scores.inc         k_clip_scores, k_clip_scores_wide, vg_clip_scores, vg_clip_scores_wide
 //                            weights by role (vit_weights), the folds (vit_fold_ln, vit_fold_conv1), vg_vit_create / _destroy / _set_weight,
 //                            the encode plan (vit_plan), one encode (VitRun, vg_vit_encode), the kernel-level test entry points
 //                            (vg_attention*, vg_gemm*), vg_vit_profile*
+//     vit_text.inc           the CLIP text tower on VitRun: k_text_embed, vg_text_create / _destroy / _set_weight / _workspace_bytes / _encode
 //     vit_graph.inc          the graph cache, vg_vit_classify_graph
 //   dev/*.inc                development build only (-DVG_DEV): superseded kernels, ablations, trace entry points, behind one-line hooks
 #include "common.h"
@@ -161,6 +162,7 @@ struct GemmProfile {
 struct VitWeights;
 struct vg_vit : VitTower {
     int width, layers, heads, patch, res, out_dim, dtype, T;
+    bool text = false;                     // a CLIP text tower (vg_text, vit_text.inc): T = the context length, causal attention, token-table front end
     GemmProfile prof;
     std::map<std::string, void*> w;        // device pointers (f32 or f16 depending on role)
     std::map<std::string, size_t> numel;
@@ -219,6 +221,7 @@ struct BlockWeights {
 struct TopWeights {
     const void *conv1, *conv1_1ch;                             // (#1ch: vit_fold_conv1, null until an input_kind 3 encode)
     const float *cls, *pos, *pos_1ch, *ln_pre_w, *ln_pre_b, *ln_post_w, *ln_post_b, *proj;
+    const float* tok;                                          // text tower: token_embedding.weight (ln_post_* = ln_final.*, proj = text_projection)
 };
 struct VitWeights { TopWeights top; std::vector<BlockWeights> blocks; };
 
@@ -232,11 +235,18 @@ static int vit_resolve(const vg_vit* v, VitWeights* out) {
         ok = false;
     };
     TopWeights& t = out->top;
-    get("conv1.weight", t.conv1, true);       get("class_embedding", t.cls, true);     get("positional_embedding", t.pos, true);
-    get("ln_pre.weight", t.ln_pre_w, true);   get("ln_pre.bias", t.ln_pre_b, true);
-    get("ln_post.weight", t.ln_post_w, true); get("ln_post.bias", t.ln_post_b, true);  get("proj", t.proj, true);
-    get("conv1.weight#1ch", t.conv1_1ch, false);
-    get("positional_embedding#1ch", t.pos_1ch, false);
+    t = TopWeights();
+    get("positional_embedding", t.pos, true);
+    if (v->text) {                            // model.py:288-300
+        get("token_embedding.weight", t.tok, true);
+        get("ln_final.weight", t.ln_post_w, true); get("ln_final.bias", t.ln_post_b, true); get("text_projection", t.proj, true);
+    } else {
+        get("conv1.weight", t.conv1, true);       get("class_embedding", t.cls, true);
+        get("ln_pre.weight", t.ln_pre_w, true);   get("ln_pre.bias", t.ln_pre_b, true);
+        get("ln_post.weight", t.ln_post_w, true); get("ln_post.bias", t.ln_post_b, true);  get("proj", t.proj, true);
+        get("conv1.weight#1ch", t.conv1_1ch, false);
+        get("positional_embedding#1ch", t.pos_1ch, false);
+    }
     out->blocks.resize((size_t)v->layers);
     for (int l = 0; l < v->layers; ++l) {
         BlockWeights& b = out->blocks[l];
@@ -331,6 +341,13 @@ static int vit_fold_conv1(vg_vit* v, hipStream_t st) {
     return VG_OK;
 }
 
+// the handle's events and device tensors (vg_vit_destroy, vg_text_destroy)
+static void vit_release(vg_vit* v) {
+    if (v->prof.init) for (int i = 0; i < 2 * VG_PROF_MAX; ++i) (void)hipEventDestroy(v->prof.ev[i]);
+    for (auto& kv : v->w) (void)hipFree(kv.second);
+    for (auto& kv : v->w32) (void)hipFree(kv.second);
+}
+
 #ifdef VG_DEV      // dev_vit_create and the development aids of tools/dev/vilgod_hip_dev.h: ablations, cycle-stamp traces
 #include "dev/vit_dev_entry.inc"
 #endif
@@ -370,9 +387,7 @@ int vg_vit_create(vg_vit** out, int width, int layers, int heads, int patch, int
 
 void vg_vit_destroy(vg_vit* v) {
     if (!v) return;
-    if (v->prof.init) for (int i = 0; i < 2 * VG_PROF_MAX; ++i) (void)hipEventDestroy(v->prof.ev[i]);
-    for (auto& kv : v->w) (void)hipFree(kv.second);
-    for (auto& kv : v->w32) (void)hipFree(kv.second);
+    vit_release(v);
     delete v;
 }
 
@@ -626,13 +641,8 @@ struct VitRun {
     // h = attention(qkv); cls: the class token's query row only (the first query tile)
     int attention(bool cls) const {
         const int T = v->T, H = v->heads;
-        if (v->dtype != 1) {
-            const size_t lds = ((size_t)T * 65 + (size_t)T * 64 + 16 * (size_t)T) * sizeof(float);
-            VG_MAX_DYNAMIC_LDS(k_attention_f32, 160 * 1024);
-            hipLaunchKernelGGL(k_attention_f32, dim3(n_crops * H), dim3(256), lds, st, (const float*)qkv(), (float*)h(), T, W(), H);
-            VG_LAUNCH_CHECK();
-            return VG_OK;
-        }
+        if (v->dtype != 1) return launch_attention_f32(v->text, (const float*)qkv(), (float*)h(), T, W(), H, n_crops * H, st);
+        if (v->text) return launch_attention_causal((const f16*)qkv(), (f16*)h(), T, W(), H, p.qkv_ld, n_crops * H, st);
         // measurement hook (vg_vit_profile_read_kind 2 / 3): an event pair around each attention launch
         const bool aprof = v->prof.begin(st);
         const int rc = launch_attention<false>((const f16*)qkv(), (f16*)h(), T, W(), H, p.qkv_ld, n_crops * H, nullptr, st, cls ? 1 : (T + 31) / 32, v->att);
@@ -676,13 +686,31 @@ struct VitRun {
         return head(xc, 1, d_feat);
     }
 
-    // features = ln_post(class-token rows) @ proj; rows_per_crop: distance between two crops' class rows
+    // features = ln_post(class-token rows) @ proj; rows_per_crop: distance between two crops' class rows; row_idx (text tower): the row of
+    // each item that is read instead of its first, ln_final(x[p, eot[p]]) @ text_projection
     template <typename TI>
-    int head(const TI* rows, int rows_per_crop, float* d_feat) const {
+    int head(const TI* rows, int rows_per_crop, float* d_feat, const int32_t* row_idx = nullptr) const {
         hipLaunchKernelGGL((k_head<TI>), dim3(n_crops), dim3(256), W() * sizeof(float), st, rows, top.ln_post_w, top.ln_post_b, top.proj, d_feat,
-                           rows_per_crop, W(), v->out_dim);
+                           rows_per_crop, W(), v->out_dim, row_idx);
         VG_LAUNCH_CHECK();
         return VG_OK;
+    }
+
+    // every block after the front end, then the head (the class-row last block ends with its own)
+    int blocks_and_head(const VitWeights& w, float* d_feat, const int32_t* row_idx = nullptr) const {
+        const int L = v->layers;
+        int rc;
+        for (int l = 0; l < L; ++l) {
+            const BlockWeights& b = w.blocks[l];
+            const bool last = l == L - 1, cls = last && p.cls_only_last, ln1_done = l == 0 && p.ln1_in_embed;
+            assert(!(last && p.stream == Stream::PAIR) || cls);        // the pair stream has no full-row last block (vit_plan)
+            if (!ln1_done && (rc = layernorm(b.f(LN1_W), b.f(LN1_B)))) return rc;
+            if ((rc = cls ? in_proj_cls(b) : in_proj(b, ln1_done || !folded()))) return rc;
+            if ((rc = attention(cls))) return rc;
+            if (cls) return tail_cls(b, d_feat);
+            if ((rc = tail_full(b, last))) return rc;
+        }
+        return p.stream == Stream::F16 ? head(x_h(), v->T, d_feat, row_idx) : head(x(), v->T, d_feat, row_idx);
     }
 };
 
@@ -708,19 +736,8 @@ int vg_vit_encode(vg_vit* v, const void* d_crops, int input_kind, int n_crops, v
     if ((rc = vit_weights(v, &w))) return rc;
     if (input_kind == 3 && (!w->top.conv1_1ch || !w->top.pos_1ch)) return VG_ERR_ARG;
     const VitRun r{v, p, w->top, st, n_crops, (char*)d_workspace};
-    const int L = v->layers;
-    if ((rc = r.embed(d_crops, input_kind, L ? &w->blocks[0] : nullptr))) return rc;
-    for (int l = 0; l < L; ++l) {
-        const BlockWeights& b = w->blocks[l];
-        const bool last = l == L - 1, cls = last && p.cls_only_last, ln1_done = l == 0 && p.ln1_in_embed;
-        assert(!(last && p.stream == Stream::PAIR) || cls);        // the pair stream has no full-row last block (vit_plan)
-        if (!ln1_done && (rc = r.layernorm(b.f(LN1_W), b.f(LN1_B)))) return rc;
-        if ((rc = cls ? r.in_proj_cls(b) : r.in_proj(b, ln1_done || !r.folded()))) return rc;
-        if ((rc = r.attention(cls))) return rc;
-        if (cls) return r.tail_cls(b, d_feat);
-        if ((rc = r.tail_full(b, last))) return rc;
-    }
-    return p.stream == Stream::F16 ? r.head(r.x_h(), v->T, d_feat) : r.head(r.x(), v->T, d_feat);
+    if ((rc = r.embed(d_crops, input_kind, v->layers ? &w->blocks[0] : nullptr))) return rc;
+    return r.blocks_and_head(*w, d_feat);
 }
 
 /* k_attention_f16 alone: softmax(q k^T / 8) v per (crop, head) on the padded qkv rows in_proj writes (model.py:175-187 via
@@ -746,12 +763,20 @@ int vg_attention_rows(int dtype, const void* d_qkv, void* d_out, int n_crops, in
     if (dtype != 0) return VG_ERR_ARG;
     // k_attention_f32 hard-codes ld = 3 W and computes every row; its K, V and probability rows must fit the LDS it requests (vg_vit_create)
     if (ld != 3 * W || q_tiles != (T + 31) / 32) return VG_ERR_ARG;
-    const size_t lds = ((size_t)T * 65 + (size_t)T * 64 + 16 * (size_t)T) * sizeof(float);
-    if (lds > 160 * 1024) return VG_ERR_ARG;
-    VG_MAX_DYNAMIC_LDS(k_attention_f32, 160 * 1024);
-    hipLaunchKernelGGL(k_attention_f32, dim3(n_crops * heads), dim3(256), lds, st, (const float*)d_qkv, (float*)d_out, T, W, heads);
-    VG_LAUNCH_CHECK();
-    return VG_OK;
+    return launch_attention_f32(false, (const float*)d_qkv, (float*)d_out, T, W, heads, n_crops * heads, st);
+}
+
+/* The causal attention of the text tower, alone (test entry point; header: vilgod_hip.h): row q sees keys 0 .. q (model.py:320-326).
+ * dtype 1: k_attention_f16<CAUSAL>, every query tile; dtype 0: k_attention_f32<CAUSAL>. */
+int vg_attention_causal_rows(int dtype, const void* d_qkv, void* d_out, int n_items_crops, int T, int W, int heads, int ld, void* stream) {
+    if (!d_qkv || !d_out || n_items_crops <= 0 || T < 1 || heads <= 0 || heads * 64 != W || ld < 3 * W) return VG_ERR_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == 1) {
+        if (T > AT_MAXT || ld % 8) return VG_ERR_ARG;
+        return launch_attention_causal((const f16*)d_qkv, (f16*)d_out, T, W, heads, ld, n_items_crops * heads, st);
+    }
+    if (dtype != 0 || ld != 3 * W) return VG_ERR_ARG;
+    return launch_attention_f32(true, (const float*)d_qkv, (float*)d_out, T, W, heads, n_items_crops * heads, st);     // (T <= 282: its LDS bound)
 }
 
 /* C = X @ Wt^T (+ epilogue), exposed for unit tests / micro-benchmarks of the GEMM itself.
@@ -860,4 +885,5 @@ int vg_vit_profile_read(vg_vit* v, int32_t* h_launches, double* h_ms, double* h_
 
 }  // extern "C"
 
+#include "vit_text.inc"
 #include "vit_graph.inc"

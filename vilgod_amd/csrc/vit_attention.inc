@@ -1,5 +1,5 @@
-// Part of vit.hip (included in place): the attention kernels (k_attention_f16, k_attention_f16_long, k_attention_f32) and the fp16
-// launch path (launch_attention).
+// Part of vit.hip (included in place): the attention kernels (k_attention_f16, k_attention_f16_long, k_attention_f32; the first and the
+// last also in a causal form for the text tower) and their launch paths (launch_attention, launch_attention_causal, launch_attention_f32).
 
 
 // ---------------------------------------------------------------------------------------------
@@ -27,7 +27,12 @@ typedef short s16x4v __attribute__((__vector_size__(4 * sizeof(short))));
 // vector work beside the other's matrix work.  Same instructions per wave on the same data: bit-identical output.  Alone, 337 crops, variants
 // interleaved in one process: 96.0 us against 99.4 (331 crops: 94.7 / 98.2).  Measured and dropped: waves 4-6 ALSO deferring their output
 // phase to the start of the next item (the guide's full recipe; accumulators kept across the barrier): 98.3 us, no better than no stagger.
-template <bool TRACE = false, int NKB = 7, int TT = 0, bool TR = false, bool STAG = false>
+// CAUSAL (the CLIP text tower, model.py:320-326 build_attention_mask): query row q sees keys 0 .. q.  Wave w's rows are [32w, 32w + 32), so
+// key blocks kb > w are wholly masked: never multiplied, exponentiated or fed to the P V MFMAs.  Block kb == w holds the diagonal: registers
+// with key > q are set to -inf before the max (a stored row has q < T, so the key >= T mask is implied), exp2(-inf) = 0 enters the sum and P
+// as an exact zero, and key 0 is always visible: sum > 0.  Row i therefore equals, bit for bit, row i of the plain kernel run on the item's
+// first i + 1 tokens.  With CAUSAL = false every added condition folds away at compile time.
+template <bool TRACE = false, int NKB = 7, int TT = 0, bool TR = false, bool STAG = false, bool CAUSAL = false>
 __global__ __launch_bounds__(448) void k_attention_f16(const f16* __restrict__ qkv, f16* __restrict__ out, int T_arg,
                                                        int W, int heads, int ld, int n_items, long long* __restrict__ trace = nullptr,
                                                        int q_tiles = 7) {
@@ -50,6 +55,8 @@ __global__ __launch_bounds__(448) void k_attention_f16(const f16* __restrict__ q
     const int q0 = wave * 32;
     const int q = q0 + r31;
     constexpr int nkb = NKB;                                          // == (T + 31) / 32, checked by the launcher
+    const int wv = CAUSAL ? __builtin_amdgcn_readfirstlane(wave) : wave;      // (the causal block skip branches on it: wave-uniform by construction)
+#define AT_LIVE(kb) ((kb) < nkb && (!CAUSAL || (kb) <= wv))          // key block kb holds keys that this wave's rows see
     static_assert(AT_MAXT * 8 == 4 * 448, "staging split");
     // PERSISTENT workgroups (182 VGPRs and 62 KB of LDS allow one 7-wave workgroup per CU, so nothing else would hide
     // an item's load latency): item = (crop, head); the NEXT item's Q / K / V rows are fetched into registers while
@@ -129,7 +136,7 @@ __global__ __launch_bounds__(448) void k_attention_f16(const f16* __restrict__ q
     for (int kb = 0; kb < 7; ++kb) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) sacc[kb][r] = 0.f;
-        if (kb < nkb) {
+        if (AT_LIVE(kb)) {
 #pragma unroll
             for (int s = 0; s < 4; ++s) {
                 f16x8 kf = *(const f16x8*)(Ks + (kb * 32 + r31) * AT_KLD + s * 16 + hh * 8);
@@ -144,14 +151,21 @@ __global__ __launch_bounds__(448) void k_attention_f16(const f16* __restrict__ q
     float mx = -INFINITY;
 #pragma unroll
     for (int kb = 0; kb < 7; ++kb) {
-        if (kb == nkb - 1) {
+        if (!CAUSAL && kb == nkb - 1) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int key = kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
                 if (key >= T) sacc[kb][r] = -INFINITY;
             }
         }
-        if (kb < nkb) {
+        if (CAUSAL && kb < nkb && kb == wv) {                          // the diagonal block: keys behind the row's own position
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int key = kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
+                if (key > q) sacc[kb][r] = -INFINITY;
+            }
+        }
+        if (AT_LIVE(kb)) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) mx = fmaxf(mx, sacc[kb][r]);
         }
@@ -166,10 +180,10 @@ __global__ __launch_bounds__(448) void k_attention_f16(const f16* __restrict__ q
     const int tail = T - 32 * (nkb - 1);
 #pragma unroll
     for (int kb = 0; kb < 7; ++kb) {
-        if (kb < nkb) {
+        if (AT_LIVE(kb)) {
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
-                if (kb < nkb - 1 || 8 * g < tail) {
+                if (CAUSAL || kb < nkb - 1 || 8 * g < tail) {
 #pragma unroll
                     for (int r = 4 * g; r < 4 * g + 4; ++r) {
                         const float p = __builtin_amdgcn_exp2f(fmaf(sacc[kb][r], c2, mc));      // raw v_exp_f32: exp2(-inf) = 0
@@ -194,10 +208,10 @@ __global__ __launch_bounds__(448) void k_attention_f16(const f16* __restrict__ q
         for (int r = 0; r < 16; ++r) oacc[dt][r] = 0.f;
 #pragma unroll
     for (int kb = 0; kb < 7; ++kb) {
-        if (kb < nkb) {
+        if (AT_LIVE(kb)) {
 #pragma unroll
             for (int s = 0; s < 2; ++s) {
-                if (kb == nkb - 1 && 16 * s >= tail) continue;         // k-step of keys that do not exist: P = 0 there, adds exact zeros
+                if (!CAUSAL && kb == nkb - 1 && 16 * s >= tail) continue;        // k-step of keys that do not exist: P = 0 there, adds exact zeros
                 f16x8 pf;
 #pragma unroll
                 for (int j = 0; j < 8; ++j) pf[j] = (f16)sacc[kb][8 * s + j];
@@ -247,6 +261,7 @@ __global__ __launch_bounds__(448) void k_attention_f16(const f16* __restrict__ q
         for (int i = 0; i < 8; ++i) o[i] = tr[i];
     }
 #undef AT_STAMP
+#undef AT_LIVE
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -453,6 +468,10 @@ __global__ __launch_bounds__(256, 2) void k_attention_f16_long(const f16* __rest
 // pipeline.  With the whole staging phase gone the item is as long as before: it is bound by the two waves that share a SIMD (seven
 // waves on four SIMDs: 2 : 2 : 2 : 1) issuing their softmax and MFMA streams one after the other, not by getting K and V into LDS.
 // fp32 parity-mode attention: one workgroup per (crop, head); K,V in LDS; one wave per query row at a time.
+// CAUSAL (the text tower): row q sees keys 0 .. q.  A wave's four rows share their key loops, bounded by the last
+// of the four (Tk); per row the keys behind its own position stay out of the max and the sum and enter P V as exact zeros, so the fmaf chain
+// over the visible keys is the plain kernel's: row i equals, bit for bit, row i of k_attention_f32 on the item's first i + 1 tokens.
+template <bool CAUSAL = false>
 __global__ __launch_bounds__(256) void k_attention_f32(const float* __restrict__ qkv, float* __restrict__ out, int T,
                                                        int W, int heads) {
     extern __shared__ float sm[];
@@ -483,7 +502,8 @@ __global__ __launch_bounds__(256) void k_attention_f32(const float* __restrict__
         float mx[QB];
 #pragma unroll
         for (int j = 0; j < QB; ++j) mx[j] = -INFINITY;
-        for (int k0 = 0; k0 < T; k0 += 64) {
+        const int Tk = CAUSAL ? (q0 + QB < T ? q0 + QB : T) : T;            // keys that any of the four rows sees
+        for (int k0 = 0; k0 < Tk; k0 += 64) {
             const int key = k0 + lane;
             const float* kr = Ks + (key < T ? key : T - 1) * 65;
             float sacc[QB] = {0.f, 0.f, 0.f, 0.f};
@@ -494,11 +514,11 @@ __global__ __launch_bounds__(256) void k_attention_f32(const float* __restrict__
                 for (int j = 0; j < QB; ++j)
                     sacc[j] = fmaf(__builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, qd[j]), d)), kv, sacc[j]);
             }
-            if (key < T) {
+            if (key < Tk) {
 #pragma unroll
                 for (int j = 0; j < QB; ++j) {
                     P[j * T + key] = sacc[j];
-                    mx[j] = fmaxf(mx[j], sacc[j]);
+                    if (!CAUSAL || key <= q0 + j) mx[j] = fmaxf(mx[j], sacc[j]);
                 }
             }
         }
@@ -507,20 +527,22 @@ __global__ __launch_bounds__(256) void k_attention_f32(const float* __restrict__
         for (int j = 0; j < QB; ++j) {
             mx[j] = vg_wave_max(mx[j]);
             float sj = 0.f;
-            for (int key = lane; key < T; key += 64) {
+            const int Tj = CAUSAL ? (q0 + j + 1 < Tk ? q0 + j + 1 : Tk) : T;     // keys that row q0 + j sees
+            for (int key = lane; key < Tj; key += 64) {
                 const float p = expf(P[j * T + key] - mx[j]);
                 P[j * T + key] = p;
                 sj += p;
             }
+            if (CAUSAL) for (int key = Tj + lane; key < Tk; key += 64) P[j * T + key] = 0.f;    // (at most three: the rows behind it in the group)
             sum[j] = vg_wave_sum(sj);
         }
         __builtin_amdgcn_s_waitcnt(0);
         float o[QB] = {0.f, 0.f, 0.f, 0.f};
-        for (int k0 = 0; k0 < T; k0 += 64) {
+        for (int k0 = 0; k0 < Tk; k0 += 64) {
             float pv[QB];
 #pragma unroll
-            for (int j = 0; j < QB; ++j) pv[j] = k0 + lane < T ? P[j * T + k0 + lane] : 0.f;
-            const int nk = T - k0 < 64 ? T - k0 : 64;
+            for (int j = 0; j < QB; ++j) pv[j] = k0 + lane < Tk ? P[j * T + k0 + lane] : 0.f;
+            const int nk = Tk - k0 < 64 ? Tk - k0 : 64;
             if (nk == 64) {
 #pragma unroll
                 for (int kk = 0; kk < 64; ++kk) {
@@ -545,9 +567,9 @@ __global__ __launch_bounds__(256) void k_attention_f32(const float* __restrict__
 
 // one short-sequence attention launch (T <= AT_MAXT): 7 waves per workgroup, at most 256 persistent workgroups
 struct AttArgs { const f16* qkv; f16* out; int T, W, heads, ld, items; long long* trace; hipStream_t st; int q_tiles; };
-template <bool TRACE, int NKB, int TT = 0, bool TR = false, bool STAG = false>
+template <bool TRACE, int NKB, int TT = 0, bool TR = false, bool STAG = false, bool CAUSAL = false>
 static int launch_attention_short(const AttArgs& a) {
-    auto kern = k_attention_f16<TRACE, NKB, TT, TR, STAG>;
+    auto kern = k_attention_f16<TRACE, NKB, TT, TR, STAG, CAUSAL>;
     const int lds = TR ? AT_LDS_BYTES_TR : AT_LDS_BYTES;
     VG_MAX_DYNAMIC_LDS(kern, lds);
     hipLaunchKernelGGL(kern, dim3(a.items < 256 ? a.items : 256), dim3(448), lds, a.st, a.qkv, a.out, a.T, a.W, a.heads, a.ld, a.items, a.trace,
@@ -586,4 +608,35 @@ static int launch_attention(const f16* qkv, f16* out, int T, int W, int heads, i
         case 6: return launch_attention_short<TRACE, 6>(a);
         default: return launch_attention_short<TRACE, 7>(a);
     }
+}
+
+// the causal form (text tower, T <= AT_MAXT): every query tile, the transposed V image, no token-count constant
+static int launch_attention_causal(const f16* qkv, f16* out, int T, int W, int heads, int ld, int items, hipStream_t st) {
+    const int nkb = (T + 31) / 32;
+    if (T < 1 || T > AT_MAXT) return VG_ERR_ARG;
+    const AttArgs a{qkv, out, T, W, heads, ld, items, nullptr, st, nkb};
+    switch (nkb) {
+        case 1: return launch_attention_short<false, 1, 0, false, false, true>(a);
+        case 2: return launch_attention_short<false, 2, 0, false, false, true>(a);
+        case 3: return launch_attention_short<false, 3, 0, false, false, true>(a);
+        case 4: return launch_attention_short<false, 4, 0, false, false, true>(a);
+        case 5: return launch_attention_short<false, 5, 0, false, false, true>(a);
+        case 6: return launch_attention_short<false, 6, 0, false, false, true>(a);
+        default: return launch_attention_short<false, 7, 0, false, false, true>(a);
+    }
+}
+
+// k_attention_f32 (plain / causal): one workgroup per item; K, V and four probability rows per wave within the 160 KiB it requests
+static int launch_attention_f32(bool causal, const float* qkv, float* out, int T, int W, int heads, int items, hipStream_t st) {
+    const size_t lds = ((size_t)T * 65 + (size_t)T * 64 + 16 * (size_t)T) * sizeof(float);
+    if (T < 1 || lds > 160 * 1024) return VG_ERR_ARG;
+    if (causal) {
+        VG_MAX_DYNAMIC_LDS(k_attention_f32<true>, 160 * 1024);
+        hipLaunchKernelGGL(k_attention_f32<true>, dim3(items), dim3(256), lds, st, qkv, out, T, W, heads);
+    } else {
+        VG_MAX_DYNAMIC_LDS(k_attention_f32<false>, 160 * 1024);
+        hipLaunchKernelGGL(k_attention_f32<false>, dim3(items), dim3(256), lds, st, qkv, out, T, W, heads);
+    }
+    VG_LAUNCH_CHECK();
+    return VG_OK;
 }

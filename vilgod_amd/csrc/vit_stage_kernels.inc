@@ -224,14 +224,17 @@ __global__ __launch_bounds__(256) void k_layernorm(const TI* __restrict__ x, con
 
 // ---------------------------------------------------------------------------------------------
 // head: ln_post(x[crop, 0, :]) @ proj  (model.py:235-238).  one workgroup per crop.
+// row_idx (text tower, model.py:352-354): row row_idx[crop] of the item's T rows instead of row 0, clamped into [0, T) -- a wrong index
+// reads a wrong row, never outside the item.
 template <typename TI>
 __global__ __launch_bounds__(256) void k_head(const TI* __restrict__ x, const float* __restrict__ lw,
                                               const float* __restrict__ lb, const float* __restrict__ proj,
-                                              float* __restrict__ feat, int T, int W, int D) {
+                                              float* __restrict__ feat, int T, int W, int D, const int32_t* __restrict__ row_idx = nullptr) {
     extern __shared__ float sm[];   // [W]
     __shared__ float red[8];
     const int crop = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const TI* src = x + (size_t)crop * T * W;
+    const int r = row_idx ? row_idx[crop] : 0;
+    const TI* src = x + ((size_t)crop * T + (r < 0 ? 0 : r >= T ? T - 1 : r)) * W;
     float s = 0.f;
     for (int c = tid; c < W; c += 256) s += (float)src[c];
     s = vg_wave_sum(s);

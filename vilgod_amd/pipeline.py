@@ -105,7 +105,7 @@ class PseudoLabelPipeline:
     def __init__(self, preprocessor_cfg=None, device='cuda:0', vit_dtype='f16', n_views=4, max_points=300_000,
                  clip_model_path='../models/clip/', min_range=1.5, z_offset=1.723, plane_seed=666, clip=None,
                  box_mode='reference', box_workers=4, vit_graph=False, angle_mode='reference', cu_reserve=None, cu_tower=None,
-                 hierarchy=None, pack='host', image_size=224):
+                 hierarchy=None, pack='host', image_size=224, text='host', text_dtype='f32'):
         cfg = preprocessor_cfg if preprocessor_cfg is not None else default_preprocessor_cfg()
         self.cfg = cfg
         self.device = torch.device(device)
@@ -141,7 +141,9 @@ class PseudoLabelPipeline:
         self.projection = RealisticProjection(_get(cfg, 'lidar_image_projection'), device=self.device,
                                               views=VIEWS_4 if n_views == 4 else VIEWS_6, angle_mode=angle_mode)
         clip_cfg = _get(cfg, 'clip')
-        self.clip = clip if clip is not None else ClipWrapper(clip_cfg, clip_model_path, device=self.device, dtype=vit_dtype)
+        # text: where the class prompts' features are computed at start-up (ClipWrapper: 'host' torch + cache file, 'device' the GPU text tower)
+        self.clip = clip if clip is not None else ClipWrapper(clip_cfg, clip_model_path, device=self.device, dtype=vit_dtype,
+                                                              text=text, text_dtype=text_dtype)
         self.vit_dtype = vit_dtype
         # `classification.image_size` (zero_shot_detector.py:405-410): 224 = the renderer's own crops; 65 .. 448 go through
         # vg_clip_preprocess (projection.render_frame), others are refused here

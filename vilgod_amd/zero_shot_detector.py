@@ -177,7 +177,8 @@ class ZeroShotDetector:
                                            z_offset=ga['z_offset'], plane_seed=dev.get('plane_seed', 666), clip=clip_model,
                                            box_mode=dev.get('box_mode', 'reference'), box_workers=dev.get('box_workers', 4),
                                    angle_mode=dev.get('angle_mode', 'reference'), vit_graph=bool(dev.get('vit_graph', False)),
-                                           hierarchy=dev.get('hierarchy', None), pack=dev.get('pack', 'host'))
+                                           hierarchy=dev.get('hierarchy', None), pack=dev.get('pack', 'host'),
+                                           text=dev.get('text', 'host'), text_dtype=dev.get('text_dtype', 'f32'))
         self.pipe = pipeline
         if 'needs_entropy' in getattr(pipeline, '_filters', {}):
             PseudoLabelPipeline.check_filter_stages(pipeline._filters, list(cfg.pipeline_active))
