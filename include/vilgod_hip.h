@@ -585,6 +585,34 @@ int vg_cluster_lshape(const float* d_points, int stride, const int32_t* d_index,
                       int criterion, const double* d_angle_table, int n_angles, double delta_zero, double* d_work,
                       double* d_box7, double* d_aux, void* stream);
 
+/* Rotated-box IoU: pcdet's boxes_iou3d_gpu / boxes_iou_bev, which the reference calls in src/utils/tracking_utils.py:9-20,
+ * src/vilgod/zero_shot_detector.py:737-739 and src/datasets/waymo_dataset.py:300.  Boxes are rows of 7 values
+ * {x, y, z, dx, dy, dz, heading}, float32 (dtype VG_IOU_F32, widened exactly) or float64 (VG_IOU_F64); all arithmetic is float64.
+ * Grouped: one call covers n_groups independent matrices.  Group g pairs the a rows [a_off[g], a_off[g+1]) with the b rows
+ * [b_off[g], b_off[g+1]) and writes its row-major [na_g, nb_g] matrix at d_out + out_off[g].  a_off / b_off: n_groups + 1 entries,
+ * non-decreasing; out_off: n_groups entries, >= 0, each group's range behind the one before (gaps allowed).  Elements of d_out that
+ * belong to no group are never written.  The plain N x M call is n_groups = 1.
+ *   mode VG_IOU_3D        BEV intersection area x z overlap / (vol_a + vol_b - intersection); 0 where the union is not positive
+ *        VG_IOU_BEV       BEV intersection area / (area_a + area_b - intersection); z and dz are not read
+ *        VG_IOU_BEV_AREA  the BEV intersection area
+ * Exactly 0.0 for an extent <= 0 (dx, dy; dz too in mode VG_IOU_3D), for no z overlap (VG_IOU_3D) and for centres farther apart than
+ * the half-diagonals allow.  |heading| < 1.6e6 (beyond: NaN).  The geometry is formed relative to b's centre, so the value does not
+ * depend on where the pair stands.
+ * vg_boxes_iou3d: device pointers; reads the three offset tables back first (one stream synchronisation; not capturable into a
+ * graph), then one launch with one lane per output element.  vg_boxes_iou3d_host: the same per-pair code (csrc/iou_pair.inc)
+ * over host arrays, no GPU needed; the two agree bit for bit.
+ * VG_ERR_ARG: dtype or mode unknown, n_groups < 0, offsets that break the rules above, null pointers with non-empty work.
+ * n_groups == 0 or only empty groups: VG_OK, nothing launched (d_a / d_b / d_out may then be NULL). */
+#define VG_IOU_F32 0
+#define VG_IOU_F64 1
+#define VG_IOU_3D 0
+#define VG_IOU_BEV 1
+#define VG_IOU_BEV_AREA 2
+int vg_boxes_iou3d(int dtype, const void* d_a, const int32_t* d_a_off, const void* d_b, const int32_t* d_b_off,
+                   int n_groups, const int64_t* d_out_off, int mode, double* d_out, void* stream);
+int vg_boxes_iou3d_host(int dtype, const void* h_a, const int32_t* h_a_off, const void* h_b, const int32_t* h_b_off,
+                        int n_groups, const int64_t* h_out_off, int mode, double* h_out);
+
 /* Detection.cluster_mass_center (src/dataclass/objects.py:121-123: np.median(cluster_points, axis=0)) of every packed cluster over the
  * first n_cols columns of the point rows (the tracker reads all five: src/vilgod/tracker.py:52-59, objects.py:238-306).  Exact
  * order statistics; an even count gives the float32 mean of the two middle values like np.median.  d_median: [n_clusters, n_cols] f32. */

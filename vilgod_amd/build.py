@@ -34,6 +34,7 @@ SOURCES = {
     'hdbscan_device.hip': ['-ffp-contract=off'],
     'segment.hip': ['-ffp-contract=off'],
     'lshape.hip': ['-ffp-contract=off'],
+    'iou.hip': ['-ffp-contract=off'],
     'pack.hip': [],
     'vit.hip': [],
 }

@@ -106,6 +106,34 @@ def iou3d_matrix(a, b):
     return out
 
 
+IOU_BACKENDS = ('host', 'device')
+
+
+def _check_iou_backend(iou):
+    if iou not in IOU_BACKENDS:
+        raise ValueError(f"iou must be one of {IOU_BACKENDS}, not {iou!r}")
+    return iou
+
+
+def iou3d_matrices_device(pairs):
+    """[(a [na,>=7], b [nb,>=7]), ...] -> [float64 [na,nb], ...]: every matrix of the list in ONE launch of the rotated-box IoU kernel
+    (vilgod_amd/iou.py iou_groups, csrc/iou.hip).  Float32 boxes are widened exactly, as iou3d_matrix widens them."""
+    import torch
+    from .iou import iou_groups
+    pairs = [tuple(np.asarray(x).reshape(-1, np.shape(x)[-1] if np.ndim(x) == 2 else 7)[:, :7] for x in ab) for ab in pairs]
+    if not pairs:
+        return []
+    dt = np.float32 if all(x.dtype == np.float32 for ab in pairs for x in ab) else np.float64
+    a_off = np.cumsum([0] + [len(a) for a, _ in pairs])
+    b_off = np.cumsum([0] + [len(b) for _, b in pairs])
+    a_all = np.concatenate([a for a, _ in pairs]).astype(dt, copy=False)
+    b_all = np.concatenate([b for _, b in pairs]).astype(dt, copy=False)
+    flat, out_off = iou_groups(torch.from_numpy(np.ascontiguousarray(a_all)).cuda(), a_off,
+                               torch.from_numpy(np.ascontiguousarray(b_all)).cuda(), b_off)
+    flat = flat.cpu().numpy()
+    return [flat[o:o + len(a) * len(b)].reshape(len(a), len(b)) for o, (a, b) in zip(out_off, pairs)]
+
+
 # ---- the adapters' `evaluation` up to the metric (pinned) -----------------------------------------------------------------------
 def _in_range(boxes, eval_range):
     corners = boxes_to_corners_3d(np.asarray(boxes)[:, :7])
@@ -115,7 +143,9 @@ def _in_range(boxes, eval_range):
 
 def filter_for_evaluation(dataset, det_annos, class_names, **kwargs):
     """-> (eval_det_annos, eval_gt_annos): waymo_dataset.py:229-320 / argo2_dataset.py:309-366 (`style` picks the variant:
-    the Argoverse adapter drops 'unknown' ground truth here and has no IoU-based removal of detections)."""
+    the Argoverse adapter drops 'unknown' ground truth here and has no IoU-based removal of detections).
+    iou='device': the moving / static removal takes its IoU from one kernel launch over all frames instead of iou3d_matrix per frame."""
+    iou_backend = _check_iou_backend(kwargs.get('iou', 'host'))
     style = kwargs.get('style', 'argo2' if type(dataset).__name__.startswith('Argo2') else 'waymo')
     eval_range = np.asarray(kwargs.get('eval_range', dataset.point_cloud_range[[0, 1, 3, 4]]), dtype=np.float64)
     sampling_rate = kwargs.get('sampling_rate', 1)
@@ -148,6 +178,9 @@ def filter_for_evaluation(dataset, det_annos, class_names, **kwargs):
             anno['name'] = np.array([class_names[0] if name in class_names else name for name in anno['name']])
     gts = gts[::sampling_rate]
     want_moving, want_static = kwargs.get('moving', False), kwargs.get('static', False)
+    free_of = None
+    if iou_backend == 'device' and style == 'waymo' and (want_moving or want_static):
+        free_of = _free_of_other_kind(dets, gts, eval_range, want_moving, want_static, kwargs.get('bev', False))
     for a_idx, anno in enumerate(gts):
         if 'difficulty' not in anno or anno['difficulty'] is None:
             anno['difficulty'] = np.ones(len(anno['name']))
@@ -167,8 +200,11 @@ def filter_for_evaluation(dataset, det_annos, class_names, **kwargs):
                 if want_moving or want_static:
                     d = dets[a_idx]
                     other = np.array(anno['gt_boxes_lidar'])[check]
-                    iou = iou3d_matrix(np.asarray(d['boxes_lidar'], np.float32), np.asarray(other, np.float32))
-                    free = iou.sum(axis=1) == 0
+                    if free_of is None:
+                        iou = iou3d_matrix(np.asarray(d['boxes_lidar'], np.float32), np.asarray(other, np.float32))
+                        free = iou.sum(axis=1) == 0
+                    else:
+                        free = free_of[a_idx]
                     d['boxes_lidar'], d['name'], d['score'] = (np.asarray(d[k])[free] for k in ('boxes_lidar', 'name', 'score'))
             if want_moving:
                 mask &= anno['moving']
@@ -180,6 +216,28 @@ def filter_for_evaluation(dataset, det_annos, class_names, **kwargs):
             gts[a_idx]['gt_boxes_lidar'][..., 2] = 0.0
             gts[a_idx]['gt_boxes_lidar'][..., 5] = 1.0
     return dets, gts
+
+
+def _free_of_other_kind(dets, gts, eval_range, want_moving, want_static, bev):
+    """Per frame with ground truth, the detections that overlap no in-range ground truth of the kind that is NOT evaluated (the `free`
+    mask of filter_for_evaluation's loop), from one launch over all frames.  Reads only: the loop applies its own changes to `gts`."""
+    frames, pairs = [], []
+    for a_idx, anno in enumerate(gts):
+        if len(anno['gt_boxes_lidar']) == 0:
+            continue
+        boxes = np.array(anno['gt_boxes_lidar'])
+        if bev:
+            boxes[..., 2] = 0.0
+            boxes[..., 5] = 1.0
+        check = _in_range(boxes, eval_range)
+        if want_moving:
+            check &= ~anno['moving']
+        if want_static:
+            check &= anno['moving']
+        det = np.asarray(dets[a_idx]['boxes_lidar'], np.float32)
+        frames.append(a_idx)
+        pairs.append((det.reshape(-1, det.shape[-1] if det.ndim == 2 else 7), np.asarray(boxes[check], np.float32)))
+    return {a_idx: m.sum(axis=1) == 0 for a_idx, m in zip(frames, iou3d_matrices_device(pairs))}
 
 
 def limit_period(val, offset=0.5, period=np.pi):
@@ -259,8 +317,10 @@ def _average_precision(precision, recall):
     return float(np.sum((r - r_next) * p))
 
 
-def detection_metrics(pd_frame, pd_box, pd_type, pd_score, gt_frame, gt_box, gt_type, gt_difficulty, config):
-    """-> {'<BREAKDOWN>_<TYPE>[_<range>]_LEVEL_<L>/AP' | '/APH': [value]} (the key layout of the TF metric ops)."""
+def detection_metrics(pd_frame, pd_box, pd_type, pd_score, gt_frame, gt_box, gt_type, gt_difficulty, config, iou='host'):
+    """-> {'<BREAKDOWN>_<TYPE>[_<range>]_LEVEL_<L>/AP' | '/APH': [value]} (the key layout of the TF metric ops).
+    iou: 'host' = iou3d_matrix per (frame, type); 'device' = the IoU of every (frame, type) from one kernel launch (csrc/iou.hip)."""
+    _check_iou_backend(iou)
     cutoffs = np.asarray(config['score_cutoffs'], np.float64)
     nc = len(cutoffs)
     shards = []                                                     # (key prefix, type, r_lo, r_hi)
@@ -275,6 +335,16 @@ def detection_metrics(pd_frame, pd_box, pd_type, pd_score, gt_frame, gt_box, gt_
     pd_rng = np.linalg.norm(np.asarray(pd_box)[:, :3], axis=1) if len(pd_box) else np.zeros(0)
     gt_rng = np.linalg.norm(np.asarray(gt_box)[:, :3], axis=1) if len(gt_box) else np.zeros(0)
     frames = np.union1d(np.unique(pd_frame), np.unique(gt_frame))
+    from_device = None
+    if iou == 'device':                                             # the groups the loop below walks, in its order, in one launch
+        groups = []
+        for f in frames:
+            pi_f, gi_f = np.flatnonzero(pd_frame == f), np.flatnonzero(gt_frame == f)
+            for t in (1, 2, 3, 4):
+                pi, gi = pi_f[pd_type[pi_f] == t], gi_f[gt_type[gi_f] == t]
+                if len(pi) or len(gi):
+                    groups.append((np.asarray(pd_box, np.float64)[pi], np.asarray(gt_box, np.float64)[gi]))
+        from_device = iter(iou3d_matrices_device(groups))
     for f in frames:
         pi_f, gi_f = np.flatnonzero(pd_frame == f), np.flatnonzero(gt_frame == f)
         for t in (1, 2, 3, 4):
@@ -282,8 +352,8 @@ def detection_metrics(pd_frame, pd_box, pd_type, pd_score, gt_frame, gt_box, gt_
             if len(pi) == 0 and len(gi) == 0:
                 continue
             thr = config['iou_thresholds'][t]
-            iou = iou3d_matrix(pd_box[pi], gt_box[gi])
-            w = np.where((iou >= thr) & (iou > 0), iou, 0.0)
+            iou_ft = iou3d_matrix(pd_box[pi], gt_box[gi]) if from_device is None else next(from_device)
+            w = np.where((iou_ft >= thr) & (iou_ft > 0), iou_ft, 0.0)
             sc = pd_score[pi]
             g_lvl = gt_difficulty[gi]
             prev_keep, match_p = None, None
@@ -326,8 +396,9 @@ def detection_metrics(pd_frame, pd_box, pd_type, pd_score, gt_frame, gt_box, gt_
     return out
 
 
-def waymo_evaluation(prediction_infos, gt_infos, class_name, distance_thresh=100, fake_gt_infos=True, cfg=None):
-    """waymo_eval.py:197-231."""
+def waymo_evaluation(prediction_infos, gt_infos, class_name, distance_thresh=100, fake_gt_infos=True, cfg=None, iou='host'):
+    """waymo_eval.py:197-231.  iou: detection_metrics' switch."""
+    _check_iou_backend(iou)
     assert len(prediction_infos) == len(gt_infos), '%d vs %d' % (len(prediction_infos), len(gt_infos))
     pd_frame, pd_box, pd_type, pd_score, pd_nlz, _ = waymo_type_results(prediction_infos, class_name, is_gt=False)
     gt_frame, gt_box, gt_type, gt_score, _, gt_diff = waymo_type_results(gt_infos, class_name, is_gt=True, fake_gt_infos=fake_gt_infos)
@@ -335,7 +406,7 @@ def waymo_evaluation(prediction_infos, gt_infos, class_name, distance_thresh=100
     gt_box, gt_frame, gt_type, gt_score, gt_diff = mask_by_distance(distance_thresh, gt_box, gt_frame, gt_type, gt_score, gt_diff)
     if len(pd_score) and pd_score.max() > 1:
         pd_score = 1 / (1 + np.exp(-pd_score))
-    return detection_metrics(pd_frame, pd_box, pd_type, pd_score, gt_frame, gt_box, gt_type, gt_diff, build_config(**dict(cfg or {})))
+    return detection_metrics(pd_frame, pd_box, pd_type, pd_score, gt_frame, gt_box, gt_type, gt_diff, build_config(**dict(cfg or {})), iou=iou)
 
 
 def evaluate_detections(dataset, det_annos, class_names, **kwargs):
@@ -343,7 +414,8 @@ def evaluate_detections(dataset, det_annos, class_names, **kwargs):
     if kwargs.get('eval_metric', 'waymo') != 'waymo':
         raise NotImplementedError
     return waymo_evaluation(dets, gts, class_name=class_names, distance_thresh=1000,
-                            fake_gt_infos=_get(dataset.dataset_cfg, 'INFO_WITH_FAKELIDAR', False), cfg=kwargs.get('eval_cfg', {}))
+                            fake_gt_infos=_get(dataset.dataset_cfg, 'INFO_WITH_FAKELIDAR', False), cfg=kwargs.get('eval_cfg', {}),
+                            iou=kwargs.get('iou', 'host'))
 
 
 _NAMES = {'TYPE_VEHICLE': 'Vehicle', 'TYPE_PEDESTRIAN': 'Pedestrian', 'TYPE_CYCLIST': 'Cyclist'}
