@@ -6,7 +6,6 @@ host (:405-409, clip.py:79-86).  Here `render_frame` renders every cluster x vie
 HIP kernels of csrc/render.hip and returns the ViT-ready crops without leaving the GPU; `get_img`
 keeps the reference's per-call interface for parity tests.
 """
-import contextlib
 import ctypes
 
 import numpy as np
@@ -142,7 +141,12 @@ class RealisticProjection:
         seg_off: [C+1] int32 CUDA; transform_to_ego: 4x4 float64 (numpy or tensor).
         Returns crops for all C*V (cluster-major, like torch.cat of get_img results).
         image_size: `classification.image_size` (zero_shot_detector.py:405-410).  224: the renderer writes the crops itself; 65 .. 448:
-        it writes its raw images and vg_clip_preprocess resizes them as the reference and PIL do (csrc/preprocess.hip)."""
+        it writes its raw images and vg_clip_preprocess resizes them as the reference and PIL do (csrc/preprocess.hip).
+        stream: every step runs on it -- the kernels and torch's own work between them (the pose upload, the per-point cluster ids,
+        the allocations), which would otherwise go to the current stream, unordered against the kernels that read them."""
+        if stream is not None and stream != torch.cuda.current_stream(points.device):
+            with torch.cuda.stream(stream):
+                return self.render_frame(points, index, seg_off, transform_to_ego, out, stream, out_buf, image_size)
         kind = {'u8': OUT_U8, 'f32': OUT_F32, 'f16': OUT_F16, 'raw110': OUT_RAW110, 'patch16': OUT_PATCH16, 'patch16c1': OUT_PATCH16_1CH}[out]
         image_size = check_image_size(image_size)
         dev = points.device
@@ -183,9 +187,8 @@ class RealisticProjection:
         rot = torch.empty((n_clusters, 6), dtype=torch.float64, device=dev)
         check(lib.vg_cluster_median(ptr(ego), ptr(seg_off), n_clusters, ptr(med), ptr(rot), sp), 'vg_cluster_median')
         if self.angle_mode == 'reference':
-            with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
-                m = med.cpu().numpy()                                     # [C,3] float32: one small read-back per frame
-                ang = torch.from_numpy(np.arctan2(m[:, 1], m[:, 0])).to(dev)
+            m = med.cpu().numpy()                                         # [C,3] float32: one small read-back per frame
+            ang = torch.from_numpy(np.arctan2(m[:, 1], m[:, 0])).to(dev)
             check(lib.vg_cluster_rot(ptr(ang), n_clusters, ptr(rot), sp), 'vg_cluster_rot')
         # per-point cluster id from the offsets
         ar = torch.arange(ptot, device=dev, dtype=torch.int32)
