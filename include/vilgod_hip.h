@@ -613,6 +613,33 @@ int vg_boxes_iou3d(int dtype, const void* d_a, const int32_t* d_a_off, const voi
 int vg_boxes_iou3d_host(int dtype, const void* h_a, const int32_t* h_a_off, const void* h_b, const int32_t* h_b_off,
                         int n_groups, const int64_t* h_out_off, int mode, double* h_out);
 
+/* Points in boxes: pcdet's roiaware_pool3d_utils.points_in_boxes_gpu, which the reference calls in src/utils/pointcloud_utils.py:144-158
+ * (get_box_heights) and :516-522 (points_in_boxes; src/vilgod/lidar_frame.py:154-161 turns box proposals into detections with it).
+ * Per point the LOWEST index of a box that contains it, -1 when none does.  A box is a row of 7 values {cx, cy, cz, dx, dy, dz, rz},
+ * float32 (box_dtype VG_PIB_F32, widened exactly) or float64 (VG_PIB_F64); a point is the first three floats of a row of
+ * point_stride floats.  The point (x, y, z) is inside iff
+ *     fabs(z - cz) <= dz / 2                                        (the z faces belong to the box)
+ *     fabs(lx) < dx / 2 + 1e-5  and  fabs(ly) < dy / 2 + 1e-5      (strict, beyond a margin of 1e-5)
+ *     lx = sx cos(rz) + sy sin(rz), ly = -sx sin(rz) + sy cos(rz), (sx, sy) = (x - cx, y - cy)
+ * with all arithmetic in float64 (pcdet: float32) and the sine / cosine of csrc/iou_pair.inc.  The rule is positive: a NaN anywhere in
+ * the point or the box, an extent that is not >= 0 and |rz| >= 1.6e6 all mean "outside".
+ * Batched: element b reads the points [b * n_points, (b + 1) * n_points), the boxes [b * n_boxes, (b + 1) * n_boxes) and writes
+ * d_box_idx [b * n_points ..], indices counted inside the element.
+ * vg_points_in_boxes: device pointers; ONE launch on `stream` (csrc/points_in_boxes.hip: one lane per point, the boxes through LDS in
+ * chunks of VG_PIB_CHUNK), no read-back, no allocation, no synchronisation, no atomics -- it can be captured into a graph and gives the
+ * same bits on every run.  vg_points_in_boxes_host: the same per-pair code (csrc/points_in_boxes_pair.inc) over host arrays, no GPU
+ * needed; the two agree bit for bit.
+ * n_boxes == 0: every index is -1 (d_boxes may be NULL).  n_points == 0 or batch == 0: VG_OK, nothing launched, nothing read.
+ * VG_ERR_ARG (nothing launched): box_dtype unknown, a negative count, point_stride < 3, null pointers with non-empty work.
+ * VG_ERR_CAPACITY: batch > 65535 (device form). */
+#define VG_PIB_F32 0
+#define VG_PIB_F64 1
+#define VG_PIB_CHUNK 256
+int vg_points_in_boxes(int box_dtype, const float* d_points, int point_stride, int n_points, const void* d_boxes, int n_boxes,
+                       int batch, int32_t* d_box_idx, void* stream);
+int vg_points_in_boxes_host(int box_dtype, const float* h_points, int point_stride, int n_points, const void* h_boxes, int n_boxes,
+                            int batch, int32_t* h_box_idx);
+
 /* Detection.cluster_mass_center (src/dataclass/objects.py:121-123: np.median(cluster_points, axis=0)) of every packed cluster over the
  * first n_cols columns of the point rows (the tracker reads all five: src/vilgod/tracker.py:52-59, objects.py:238-306).  Exact
  * order statistics; an even count gives the float32 mean of the two middle values like np.median.  d_median: [n_clusters, n_cols] f32. */

@@ -11,6 +11,8 @@ Mirrors what `LidarFrame` (src/vilgod/lidar_frame.py:15-59, 124-147) and `Detect
 """
 import numpy as np
 
+INDEX_WO_GROUND, INDEX_ALL_POINTS = 'points_ref_wo_ground', 'points_ref'      # FrameState.index_space
+
 DETECTION_FIELDS = ['cluster_id', '_bounding_box', 'valid', 'static', 'gt_assigned', 'cluster_points_index',
                     'object_class_predictions', 'tid', 'static_track', 'object_class_predictions_detailed',
                     'object_class_predictions_score', 'object_class', 'object_class_score']       # objects.py:90-93
@@ -233,6 +235,7 @@ class FrameState:
         self.filtered = False
         self.filter_dict = {}                          # Detection.filter_dict (objects.py:168), name -> bool [C]: every active filter's own
                                                        # verdict, written only when vg_cluster_filter_ex ran (not serialised, like the reference)
+        self.index_space = INDEX_WO_GROUND             # the point table `index` refers to (set_proposals: INDEX_ALL_POINTS)
 
     @property
     def n_detections(self):
@@ -246,6 +249,46 @@ class FrameState:
         self.static = np.ones(C, bool)                 # :58
         self.tid = np.full(C, -1, np.int64)            # :64
         self.static_track = np.full(C, -1, np.int8)
+
+    def set_proposals(self, proposals_ref, box_idx, names=None):
+        """generate_detections(None, proposals=..., names=...) (lidar_frame.py:156-167, 232-248) as arrays: one detection per proposal
+        that owns at least one point.  proposals_ref [P, >=7]: the boxes in the reference frame; box_idx [n_points]: per point of
+        `points_ref` (ALL points, ground included) the proposal that owns it or -1 (points_in_boxes); alternatively the packed lists
+        (ids, index, seg_off) of that membership as `pack_clusters` returns them.  cluster_ids are the proposal indices (ascending,
+        with gaps), boxes[c] = proposals_ref[cid, :7]; with `names`, object_class['proposal'] = names[cid] shows in `detection_dict`
+        (that key of the five alone: no predictions, no score).  The lists index `points_ref`: `index_space` says so, and
+        `require_index_space` lets a stage that reads `points_ref_wo_ground` refuse the frame."""
+        proposals_ref = np.asarray(proposals_ref)
+        if proposals_ref.ndim != 2 or proposals_ref.shape[1] < 7:
+            raise ValueError('proposals_ref: [P, >=7]')
+        P = len(proposals_ref)
+        if isinstance(box_idx, tuple):
+            ids, index, seg = box_idx
+        else:
+            box_idx = np.asarray(box_idx)
+            if box_idx.ndim != 1:
+                raise ValueError('box_idx: [n_points], one proposal index (or -1) per point')
+            ids, index, seg = pack_clusters_numpy(box_idx, None, 0.0)
+        ids = np.asarray(ids, dtype=np.int64)
+        if len(ids) and (ids.min() < 0 or ids.max() >= P):
+            raise ValueError(f'box_idx: proposal indices outside 0 .. {P - 1}')
+        if names is not None and len(names) != P:
+            raise ValueError(f'names: {len(names)} entries for {P} proposals')
+        self.set_clusters(ids, np.asarray(index, dtype=np.int32), np.asarray(seg, dtype=np.int32))
+        self.index_space = INDEX_ALL_POINTS
+        self.boxes = np.array(proposals_ref[ids, :7], dtype=np.float64)
+        if names is not None:
+            C = len(ids)
+            name = np.empty(C, object)
+            name[:] = [names[int(c)] for c in ids]
+            self.cls['proposal'] = dict(has=np.ones(C, bool), name=name, name_only=True)
+
+    def require_index_space(self, space, what):
+        """ValueError unless the detections' lists index the point table `space` (INDEX_WO_GROUND / INDEX_ALL_POINTS)."""
+        have = getattr(self, 'index_space', INDEX_WO_GROUND)
+        if have != space:
+            raise ValueError(f'{what} reads {space}, but this frame\'s detections index {have} '
+                             f'({"set_proposals" if have == INDEX_ALL_POINTS else "set_clusters"} built them)')
 
     def cluster_index(self, c):
         return self.index[self.seg_off[c]:self.seg_off[c + 1]]
@@ -288,7 +331,8 @@ class FrameState:
         d['static'] = bool(self.static[c])
         d['gt_assigned'] = False
         d['cluster_points_index'] = self.cluster_index(c).astype(np.int64)
-        has = [k for k, e in self.cls.items() if e['has'][c]]
+        named = [k for k, e in self.cls.items() if e['has'][c]]
+        has = [k for k in named if not self.cls[k].get('name_only')]       # (set_proposals' entry carries object_class alone)
         if has:
             d['object_class_predictions'] = {k: self.cls[k]['pred'][c].astype(str) for k in has}
         d['tid'] = int(self.tid[c])
@@ -297,7 +341,10 @@ class FrameState:
         if has:
             d['object_class_predictions_detailed'] = {k: self.cls[k]['detailed'][c].astype(str) for k in has}
             d['object_class_predictions_score'] = {k: self.cls[k]['score'][c].copy() for k in has}
-            d['object_class'] = {k: np.str_(self.cls[k]['name'][c]) for k in has}      # an element of np.unique's result, lidar_frame.py:269-283
+        if named:
+            # an element of np.unique's result, lidar_frame.py:269-283; a proposal's name is the caller's own object (:246-247)
+            d['object_class'] = {k: self.cls[k]['name'][c] if self.cls[k].get('name_only') else np.str_(self.cls[k]['name'][c]) for k in named}
+        if has:
             d['object_class_score'] = {k: self.final_score(k, c) for k in has}
         return d
 
@@ -325,7 +372,7 @@ class FrameState:
         d.update({k: getattr(self, k).copy() for k in self._COMPACT_COPIED})
         d['boxes'] = None if self.boxes is None else self.boxes.copy()
         d['filtered'] = bool(self.filtered)
-        d['cls'] = {k: {f: v.copy() for f, v in e.items()} for k, e in self.cls.items()}
+        d['cls'] = {k: {f: v.copy() if isinstance(v, np.ndarray) else v for f, v in e.items()} for k, e in self.cls.items()}
         return d
 
     @classmethod
@@ -365,6 +412,11 @@ class FrameState:
         for k in keys:
             has = np.array([k in (d.get('object_class') or {}) for d in dets])
             rows = [d for d in dets if k in (d.get('object_class') or {})]
+            if not any(k in (r.get('object_class_predictions') or {}) for r in rows):      # a name alone: set_proposals' entry
+                name = np.empty(C, object)
+                name[np.flatnonzero(has)] = [r['object_class'][k] for r in rows]
+                self.cls[k] = dict(has=has, name=name, name_only=True)
+                continue
             self.set_classes(k, has,
                              np.array([r['object_class_predictions'][k] for r in rows], dtype=object),
                              np.array([r['object_class_predictions_detailed'][k] for r in rows], dtype=object),

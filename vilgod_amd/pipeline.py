@@ -896,10 +896,11 @@ class PseudoLabelPipeline:
 
         return self.map_workers(range(len(prepared)), run, n_workers)
 
-    def pack_device(self, labels, probs):
+    def pack_device(self, labels, probs, label_bound=None):
         """Cluster packing on the device (csrc/pack.hip) for labels / probabilities that are CUDA tensors (the device hierarchy's) or host
         arrays (host hierarchy, the two-frame clusterer: uploaded, 12 bytes per point).  Reads the 12-byte counts back -- the one
         synchronisation: it sizes every launch that follows -- and queues the lists' copy into pinned host memory.
+        label_bound: exclusive upper bound of CUDA labels that are not the hierarchy's (`label_proposals`: the number of proposals).
         -> (d_index int32 [P], d_seg int32 [C + 1], fetch) with fetch() -> (ids int64 [C], index int32 [P], seg int32 [C + 1]) numpy
         arrays of the frame's own (it waits for the copy); or None when the frame cannot be packed here (labels beyond int32 or beyond
         the bound of the call): the caller packs it on the host."""
@@ -911,6 +912,10 @@ class PseudoLabelPipeline:
             # which contains another, each of >= min_cluster_size points; allow_single_cluster adds only the root ALONE (label 0,
             # also on a frame of fewer than min_cluster_size points: the + 1)
             bound = n // max(self.cluster_model.min_cluster_size, 1) + 1
+            if label_bound is not None:
+                bound = int(label_bound)
+                if bound > PACK_MAX_LABEL_BOUND:
+                    return None
         else:
             labels = np.asarray(labels)
             n = labels.size
@@ -996,6 +1001,67 @@ class PseudoLabelPipeline:
         names, fine_names = self._name_arrays
         fs.set_classes(key, which, names[mapped], fine_names[fine], sc, names[win], final)
         return names, win, final
+
+    def label_proposals(self, points, pose, ref_pose, proposals, names=None, fnr=0, state=None):
+        """Zero-shot labels for box proposals: LidarFrame.generate_detections(None, proposals=..., names=...) (lidar_frame.py:154-161,
+        244-247) followed by the classification and the vote.  proposals: [P, >=7] boxes [x, y, z, dx, dy, dz, heading] in the EGO frame
+        (a detector's, another pipeline's, annotations); names: P entries kept as object_class['proposal'].
+        Upload, `to_ref` on ALL points (no ground pass, no clustering: the pipeline's ground state is not touched), the proposals moved
+        to the reference frame, vg_points_in_boxes (float32 boxes, as pointcloud_utils.py:516-522 casts them), the membership packed by
+        `self.pack`, FrameState.set_proposals, `classify` on the full point table, `vote_classes`.  No filter runs: every proposal that
+        owns a point is classified; the others are absent from the frame state and from the result.
+        -> (FrameState, result dict as `label`'s: boxes_lidar are the INPUT boxes of the kept rows, not refitted; moving all False;
+        restricted to class_names).  `proposal_rows(fs)` gives the proposal index of each result row."""
+        from .points_in_boxes import points_in_boxes_gpu
+        from .sequence_datasets import apply_transform
+        proposals = np.asarray(proposals)
+        if proposals.ndim != 2 or proposals.shape[1] < 7:
+            raise ValueError(f'proposals: [P, >=7] boxes, got shape {proposals.shape}')
+        if not np.issubdtype(proposals.dtype, np.floating):
+            proposals = proposals.astype(np.float64)
+        P = len(proposals)
+        if names is not None and len(names) != P:
+            raise ValueError(f'names: {len(names)} entries for {P} proposals')
+        fs = state if state is not None else FrameState(fnr, pose, ref_pose)
+        self.last_probs = torch.zeros((0, len(self.class_list)), dtype=torch.float32, device=self.device)
+        result = {'boxes_lidar': np.zeros((0, 7)), 'name': np.array([]), 'score': np.array([]), 'moving': np.array([])}
+        d_pts = self.upload(points)
+        n = fs.n_points = d_pts.shape[0]
+        proposals_ref = apply_transform(proposals, fs.transform_to_ref, box=True)          # lidar_frame.py:159
+        if P == 0 or n == 0:
+            fs.set_proposals(np.zeros((0, 7)) if P == 0 else proposals_ref, np.full(n, -1, np.int64), None if P == 0 else names)
+            return fs, result
+        d_ref = self.to_ref(d_pts, fs.transform_to_ref)
+        d_boxes = torch.from_numpy(np.ascontiguousarray(proposals_ref[:, :7], dtype=np.float32)).to(self.device)
+        d_labels = points_in_boxes_gpu(d_ref.unsqueeze(0), d_boxes.unsqueeze(0))[0]
+        packed = self.pack_device(d_labels, None, label_bound=P) if self.pack == 'device' else None
+        if packed is not None:
+            d_index, d_seg, fetch = packed
+            lists = fetch()
+        else:
+            lists = pack_clusters(d_labels.cpu().numpy(), None, 0.0)
+            d_index, d_seg = self.lists_to_device(lists[1], lists[2])
+        fs.set_proposals(proposals_ref, lists, names)
+        C = fs.n_detections
+        if C == 0:
+            return fs, result
+        probs_d, top1, score = self.classify(d_ref, d_index, d_seg, fs.transform_to_ego)
+        names_, win, final = self.vote_classes(fs, self.cls_key, np.ones(C, bool), top1.cpu().numpy(), score.cpu().numpy())
+        keep = np.array([names_[w] in self.class_names for w in win], dtype=bool)
+        result = {'boxes_lidar': np.array(proposals[fs.cluster_ids[keep], :7], dtype=np.float64),
+                  'name': np.array([str(names_[w]) for w in win[keep]]),
+                  'score': np.array(final[keep]),
+                  'moving': np.zeros(int(keep.sum()), dtype=bool)}
+        self.last_probs = probs_d
+        return fs, result
+
+    def proposal_rows(self, fs):
+        """The proposal index of every row of `label_proposals`' result dict (the detections whose voted class is in class_names)."""
+        e = fs.cls.get(self.cls_key)
+        if e is None:
+            return np.zeros(0, np.int64)
+        keep = np.array([bool(h) and nm in self.class_names for h, nm in zip(e['has'], e['name'])], dtype=bool)
+        return fs.cluster_ids[keep]
 
     def label(self, fs, d_ref, d_X, gidx, labels, probs, entropy=None, t=None, t0=None, tick=None, before_classify=None):
         """Everything after clustering: detections, static flags, filters, classification, boxes, results."""

@@ -36,7 +36,7 @@ import torch
 from . import dist as vdist
 from ._lib import PREPROCESS_IMAGE_SIZE
 from .boxes import box_method
-from .frame_state import FrameState, select_rows_device, sublist_offsets
+from .frame_state import FrameState, select_rows_device, sublist_offsets, INDEX_WO_GROUND
 from .pipeline import PseudoLabelPipeline
 
 
@@ -251,6 +251,7 @@ class ZeroShotDetector:
 
     def _cluster_lists(self, fnr, rows=None):
         fs = self.lidar_frame_list[fnr]
+        fs.require_index_space(INDEX_WO_GROUND, 'a stage of the dispatcher')       # (the stages pair these lists with points_ref_wo_ground)
         held = self._dev.get(fnr, {}).get('lists')
         if held is not None and held[0] is fs.index:
             # device.pack=device: the frame's lists never left the GPU (spatial_clustering); a subset of the clusters is cut there too
@@ -811,6 +812,7 @@ class ZeroShotDetector:
         meanwhile).  method: (name, args) of box_method, None = minimum_bounding_rectangle."""
         from .boxes import _Done
         fs = self.lidar_frame_list[fnr]
+        fs.require_index_space(INDEX_WO_GROUND, 'the box fit')
         index, seg = fs.sublists(rows)
         if method is not None and method[0] != 'minimum_bounding_rectangle':
             boxes = self.pipe.fit_boxes(X, index, seg, method={'name': method[0], 'args': method[1]})
