@@ -646,6 +646,32 @@ int vg_points_in_boxes_host(int box_dtype, const float* h_points, int point_stri
 int vg_cluster_medians(const float* d_points, int stride, int n_cols, const int32_t* d_index, const int32_t* d_seg_off, int n_clusters,
                        float* d_median, void* stream);
 
+/* Oriented extents: the per-point part of the motion-aligned boxes of moving tracks (the reference's fit_bounding_boxes_simple,
+ * src/vilgod/zero_shot_detector.py:576-603: `np.dot(pts[:, :3] - center, rot)`, its min / max per column, min / max of z).
+ * A PAIR is (cluster, direction).  Pair p reads cluster c = d_pair_cluster[p] (NULL: c = p, and then n_pairs == n_clusters), whose
+ * points are d_index[d_seg_off[c] .. d_seg_off[c + 1]), rows of `stride` floats as in vg_cluster_medians; the same cluster may sit in
+ * several pairs.  d_center3[p]: float32 {cx, cy, cz}, the cluster's median.  d_rot4[p] = {r00, r01, r10, r11}, float64: the upper-left
+ * 2 x 2 of the direction's rotation matrix exactly as the host built it (scipy's goes through a quaternion: not cos / sin).  Per point
+ *     float  dx = x - cx,  dy = y - cy;                      (float32, rounded once)
+ *     double px = fma((double)dy, r10, (double)dx * r00);    double py = fma((double)dy, r11, (double)dx * r01);
+ * which is what np.dot gives for float32 points and centre and a float64 matrix whose third row and column are (0, 0, 1).
+ * d_ext6[p] = {min px, max px, min py, max py, min z, max z}, float64, z the point's own float32 z widened; a zero is written as +0.
+ * Six NaN for: a cluster without points, a pair index outside [0, n_clusters) (no point is read), and a pair with anything
+ * non-finite in it -- a point's x, y or z, the centre, or a projection (numpy would poison only the affected columns).
+ * vg_cluster_oriented_extents: device pointers; ONE launch on `stream` (csrc/oriented_extent.hip: one workgroup of VG_OEXT_BLOCK
+ * threads per pair), no read-back, no allocation, no synchronisation, no atomics -- it can be captured into a graph; min / max do not
+ * depend on the order of reduction, so every run gives the same bits.  vg_cluster_oriented_extents_host: the same per-point code
+ * (csrc/oriented_extent_point.inc) over host arrays, no GPU needed; the two agree bit for bit.
+ * VG_ERR_ARG before any device work: a negative count, stride < 3, and with n_pairs > 0: d_pair_cluster == NULL with
+ * n_pairs != n_clusters, null pointers with non-empty work.  n_pairs == 0 (valid counts and stride): VG_OK, nothing launched. */
+#define VG_OEXT_BLOCK 1024
+int vg_cluster_oriented_extents(const float* d_points, int stride, const int32_t* d_index, const int32_t* d_seg_off, int n_clusters,
+                                const int32_t* d_pair_cluster, int n_pairs, const float* d_center3, const double* d_rot4,
+                                double* d_ext6, void* stream);
+int vg_cluster_oriented_extents_host(const float* h_points, int stride, const int32_t* h_index, const int32_t* h_seg_off, int n_clusters,
+                                     const int32_t* h_pair_cluster, int n_pairs, const float* h_center3, const double* h_rot4,
+                                     double* h_ext6);
+
 /* ---- execution resources (no reference counterpart: the reference has one implicit CUDA stream) -------------
  * A HIP stream whose kernels may only be dispatched to the compute units set in h_cu_mask (hipExtStreamCreateWithCUMask):
  * n_words 32-bit words, bit i of the mask = CU slot i.  On gfx950 in SPX mode the driver deals the mask bits round-robin over the

@@ -720,6 +720,27 @@ class PseudoLabelPipeline:
               'vg_cluster_medians')
         return out
 
+    def oriented_extents(self, d_X, d_index, d_seg, pair_cluster, center3, rot4, out=None):
+        """The oriented extents of (cluster, direction) pairs over the packed clusters (vg_cluster_oriented_extents, zero_shot_detector.py:
+        576-603): pair_cluster [n_pairs] (None: pair p is cluster p), center3 [n_pairs,3] float32, rot4 [n_pairs,4] float64 -- numpy
+        arrays (uploaded on the current stream) or CUDA tensors of those dtypes -> CUDA [n_pairs,6] float64 {min x', max x', min y', max y',
+        min z, max z}; `out`: a contiguous CUDA [n_pairs,6] float64 view to write instead.  One launch, nothing read back."""
+        from .oriented_extents import pair_arrays
+        C = d_seg.numel() - 1
+        if not all(isinstance(a, torch.Tensor) for a in (center3, rot4)) or not isinstance(pair_cluster, (torch.Tensor, type(None))):
+            pair_cluster, center3, rot4 = (None if a is None else torch.from_numpy(a).to(self.device)
+                                           for a in pair_arrays(C, pair_cluster, center3, rot4))
+        n_pairs = C if pair_cluster is None else pair_cluster.numel()
+        for name, a, dtype, shape in (('pair_cluster', pair_cluster, torch.int32, (n_pairs,)), ('center3', center3, torch.float32, (n_pairs, 3)),
+                                      ('rot4', rot4, torch.float64, (n_pairs, 4)), ('out', out, torch.float64, (n_pairs, 6))):
+            if a is not None and not (a.is_cuda and a.dtype == dtype and tuple(a.shape) == shape and a.is_contiguous()):
+                raise ValueError(f'oriented_extents: {name} must be a contiguous CUDA {dtype} tensor of shape {shape}')
+        if out is None:
+            out = torch.empty((n_pairs, 6), dtype=torch.float64, device=self.device)
+        check(lib.vg_cluster_oriented_extents(ptr(d_X), d_X.stride(0), ptr(d_index), ptr(d_seg), C, ptr(pair_cluster), n_pairs, ptr(center3),
+                                              ptr(rot4), ptr(out), stream_ptr()), 'vg_cluster_oriented_extents')
+        return out
+
     def lists_to_device(self, index, seg):
         """Packed cluster lists of the host -> (d_index, d_seg) CUDA int32, queued on the current stream."""
         return tuple(torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(self.device) for a in (index, seg))

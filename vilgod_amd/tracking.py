@@ -287,24 +287,48 @@ def motion_vectors(centers_xy, look_ahead=10, min_far=0.5, min_step=0.3, max_ang
     return out
 
 
-def moving_boxes(points_list, directions, to_ego_list, top_k=3, centers3=None):
+def direction_rotations(directions):
+    """Directions of travel of a track's entries -> (angle [n], rotation matrices [n,3,3] float64) as zero_shot_detector.py:572-575
+    builds them: np.arctan2 in the directions' dtype, then one scipy call (through a quaternion: the entries are not cos / sin)."""
+    from scipy.spatial.transform import Rotation as R
+    d = np.asarray(directions)
+    angle = np.arctan2(d[:, 1], d[:, 0])
+    return angle, R.from_euler('z', angle, degrees=False).as_matrix()
+
+
+def moving_boxes(points_list, directions, to_ego_list, top_k=3, centers3=None, extents=None, counts=None):
     """zero_shot_detector.py:572-659: a box per entry aligned with its direction of travel, all resized to the median size of the
     top_k entries with the most points and shifted so that the corner closest to the ego vehicle stays where it was.
     The rotations of a track come from one scipy call and the closest-corner shifts are array operations over the track; the
-    products that go through BLAS upstream (np.dot) stay per-entry np.dot calls so that their rounding is the same."""
-    from scipy.spatial.transform import Rotation as R
-    n = len(points_list)
-    d = np.asarray(directions)
-    angle = np.arctan2(d[:, 1], d[:, 0])
-    rots = R.from_euler('z', angle, degrees=False).as_matrix()
+    products that go through BLAS upstream (np.dot) stay per-entry np.dot calls so that their rounding is the same.
+    extents [n,6] = {min x', max x', min y', max y', min z, max z} per entry (vg_cluster_oriented_extents, which restates the
+    per-point chain of the np.dot below) with counts [n] (points per entry) and centers3: nothing here touches a point then, and
+    points_list may be None."""
+    angle, rots = direction_rotations(directions)
+    n = len(angle)
+    if extents is not None:
+        if counts is None or centers3 is None:
+            raise ValueError('moving_boxes: extents come with counts (points per entry) and centers3')
+        counts = [int(c) for c in counts]
+    else:
+        counts = [len(p) for p in points_list]
     boxes = np.empty((n, 7))
     corner_arr = np.empty((n, 4, 2))
     tops = np.empty(n)
-    for j, pts_all in enumerate(points_list):
+    for j in range(n):
         rot = rots[j]
-        center = np.median(pts_all[..., :3], axis=0) if centers3 is None else np.asarray(centers3[j], dtype=pts_all.dtype)
-        proj = np.dot(pts_all[..., :3] - center, rot)
-        mn, mx = proj.min(axis=0), proj.max(axis=0)
+        if extents is None:
+            pts_all = points_list[j]
+            center = np.median(pts_all[..., :3], axis=0) if centers3 is None else np.asarray(centers3[j], dtype=pts_all.dtype)
+            proj = np.dot(pts_all[..., :3] - center, rot)
+            mn, mx = proj.min(axis=0), proj.max(axis=0)
+            z = pts_all[:, 2]
+            zmin, zmax = z.min(), z.max()
+        else:
+            e = extents[j]
+            center = np.asarray(centers3[j], dtype=np.float32)
+            mn, mx = (e[0], e[2]), (e[1], e[3])
+            zmin, zmax = np.float32(e[4]), np.float32(e[5])             # the points' own float32 z: exact, and the height stays float32
         rect = np.array([[mx[0], mn[1]], [mn[0], mn[1]], [mn[0], mx[1]], [mx[0], mx[1]]], dtype=np.float32)
         corners = np.dot(rect, rot[:2, :2].T)
         corners += center[:2]
@@ -312,12 +336,10 @@ def moving_boxes(points_list, directions, to_ego_list, top_k=3, centers3=None):
         l = np.linalg.norm(corners[0] - corners[-1])
         c = (corners[0] + corners[2]) / 2
         corner_arr[j] = corners
-        z = pts_all[:, 2]
-        zmin, zmax = z.min(), z.max()
         height = zmax - zmin
         tops[j] = zmax
         boxes[j] = (c[0], c[1], zmin + height / 2, w, l, height, angle[j])
-    top = np.argsort([len(p) for p in points_list])[-top_k:]
+    top = np.argsort(counts)[-top_k:]
     ref = np.median(boxes[top], axis=0)
     cc = np.empty(n, dtype=np.int64)
     for i, T in enumerate(to_ego_list):
@@ -337,10 +359,12 @@ def moving_boxes(points_list, directions, to_ego_list, top_k=3, centers3=None):
     return boxes
 
 
-def moving_boxes_packed(xyz, seg, directions, to_ego, centers3):
-    """moving_boxes on packed cluster points ([P,3] + offsets): the helper-process form (vilgod_amd/box_worker.py)."""
-    pts = [xyz[seg[i]:seg[i + 1]] for i in range(len(seg) - 1)]
-    return moving_boxes(pts, list(directions), list(to_ego), centers3=None if centers3 is None else list(centers3))
+def moving_boxes_packed(xyz, seg, directions, to_ego, centers3, extents=None, counts=None):
+    """moving_boxes on packed cluster points ([P,3] + offsets): the helper-process form (vilgod_amd/box_worker.py).  With extents and
+    counts (see moving_boxes) xyz and seg are not read and may be None."""
+    pts = None if extents is not None else [xyz[seg[i]:seg[i + 1]] for i in range(len(seg) - 1)]
+    return moving_boxes(pts, list(directions), list(to_ego), centers3=None if centers3 is None else list(centers3),
+                        extents=extents, counts=counts)
 
 
 class DetectionTable:
@@ -364,7 +388,7 @@ def _entry_set(tab, t, i, field, value):
 
 
 def fit_track_boxes(tracker, tab, points_of, static_of, to_ego_of, rectangle=None, static_box_of=None, median_of=None,
-                    moving_async=None, max_pending=8):
+                    moving_async=None, max_pending=8, moving_extents=None, count_of=None):
     """The track branch of fit_bounding_boxes_simple for every valid track, in track order: boxes and `static_track` flags of
     the entries (into `tab` for real detections, into the track for its clones) and `track.static`.
     points_of(key) -> cluster points [n,>=3]; static_of(key) -> Detection.static (the entropy flag); to_ego_of(fnr) -> 4x4;
@@ -374,7 +398,15 @@ def fit_track_boxes(tracker, tab, points_of, static_of, to_ego_of, rectangle=Non
     decided first for all tracks (nothing of it reads `tab`); the entries are then written in track order, as before -- one detection
     can sit in two tracks (far-match rule), and the later track's values must win.  At most `max_pending` moving_async requests are
     outstanding (each holds its track's packed points until it is answered), and every request is answered BEFORE the first entry is
-    written: a helper that fails leaves `tab` and the tracks untouched."""
+    written: a helper that fails leaves `tab` and the tracks untouched.
+    moving_extents(pairs) -> [len(pairs), 6] oriented extents (vg_cluster_oriented_extents): called ONCE, for all moving tracks
+    together, with pairs = [(position of the track among the valid tracks, entry, key, rot4 = the direction's rotation {r00, r01, r10,
+    r11}, centre = the median's first three columns)] -- every pair is known before any box is written, because what a track needs is
+    decided first.  It needs median_of and count_of(key) -> points of the cluster (the top-k choice of moving_boxes); with it
+    points_of is never called for a moving track and moving_async is not asked."""
+    if moving_extents is not None and (median_of is None or count_of is None):
+        raise ValueError('fit_track_boxes: moving_extents needs median_of and count_of')
+    pairs = []                                           # moving_extents: the pairs of all moving tracks, in plan order
     sbox = (lambda k, p: np.array(static_box_of(k), dtype=np.float64)) if static_box_of is not None else (lambda k, p: static_box(p, rectangle))
     need_pts = static_box_of is None                     # the finished static boxes make the points of static tracks unnecessary
     plan = []
@@ -385,10 +417,13 @@ def fit_track_boxes(tracker, tab, points_of, static_of, to_ego_of, rectangle=Non
             j = pending.pop(0)
             t_, _, kind_, res_ = plan[j]
             plan[j] = (t_, None, kind_, res_.result())
-    for t in tracker.tracks_valid:
+    lazy = moving_extents is not None                    # the points of a track are gathered once it is known not to move
+    for pos, t in enumerate(tracker.tracks_valid):
         n = len(t)
-        pts = [points_of(k) for k in t.source] if need_pts else [None] * n
+        pts = [points_of(k) for k in t.source] if need_pts and not lazy else [None] * n
         if all(static_of(k) for k in t.source):
+            if need_pts and lazy:
+                pts = [points_of(k) for k in t.source]
             plan.append((t, pts, 'static', None))
             continue
         # median_of(key) -> np.median(cluster points, axis=0) (the medians track_clusters already has: vg_cluster_medians)
@@ -401,7 +436,13 @@ def fit_track_boxes(tracker, tab, points_of, static_of, to_ego_of, rectangle=Non
             med = None
             centers = np.array([np.median(p[..., :2], axis=0) for p in pts])
         dirs = motion_vectors(centers)
-        if dirs:
+        if dirs and lazy:
+            c3 = [m[:3] for m in med]
+            egos = [to_ego_of(f) for f in t.frames]
+            rot4 = direction_rotations(dirs)[1][:, :2, :2].reshape(n, 4)
+            plan.append((t, None, 'moving', (len(pairs), dirs, egos, c3)))
+            pairs.extend((pos, i, k, rot4[i], c3[i]) for i, k in enumerate(t.source))
+        elif dirs:
             if pts[0] is None:
                 pts = [points_of(k) for k in t.source]
             c3 = [m[:3] for m in med] if med is not None else None
@@ -413,7 +454,18 @@ def fit_track_boxes(tracker, tab, points_of, static_of, to_ego_of, rectangle=Non
             else:
                 plan.append((t, None, 'moving', moving_boxes(pts, dirs, egos, centers3=c3)))
         else:
+            if need_pts and lazy:
+                pts = [points_of(k) for k in t.source]
             plan.append((t, pts, 'still', None))
+    if pairs:
+        ext = np.asarray(moving_extents(pairs), dtype=np.float64)
+        if ext.shape != (len(pairs), 6):
+            raise ValueError(f'fit_track_boxes: moving_extents returned {ext.shape} for {len(pairs)} pairs')
+        for j, (t, _, kind, res) in enumerate(plan):
+            if kind == 'moving':
+                first, dirs, egos, c3 = res
+                plan[j] = (t, None, kind, moving_boxes(None, dirs, egos, centers3=c3, extents=ext[first:first + len(t)],
+                                                       counts=[count_of(k) for k in t.source]))
     settle(0)
     for t, pts, kind, res in plan:
         n = len(t)

@@ -37,6 +37,7 @@ from . import dist as vdist
 from ._lib import PREPROCESS_IMAGE_SIZE
 from .boxes import box_method
 from .frame_state import FrameState, select_rows_device, sublist_offsets, INDEX_WO_GROUND
+from .oriented_extents import moving_boxes_mode
 from .pipeline import PseudoLabelPipeline
 
 
@@ -167,6 +168,9 @@ class ZeroShotDetector:
                              "(tools/preprocess_data.py resolves 'auto' before it builds the detector)")
         if shard == 'sequences':
             self.rank, self.world_size = 0, 1            # whole sequences per rank (tools/preprocess_data.py): nothing is exchanged inside one
+        # device.moving_boxes: where the points of moving tracks are measured for their motion-aligned boxes -- host (gathered per entry,
+        # numpy in the box helper processes) or device (vg_cluster_oriented_extents: one launch per frame, no host copy of the points)
+        self.moving_boxes = moving_boxes_mode(dev.get('moving_boxes'))
         if pipeline is None:
             margs = [t for t in cfg.pipeline if t['name'] == 'mask_ground_points']
             ga = margs[0]['args'] if margs else {'min_range': 1.5, 'z_offset': 1.723}
@@ -410,8 +414,8 @@ class ZeroShotDetector:
     def back_is_host_only(self):
         """After process('front'): does the `back` part stay off the GPU?  The box stage does only when every precondition of its
         host-only route holds -- checked here, not assumed: the tracker has valid tracks, the boxes come from the helper
-        processes (box_mode 'reference'), every tracked (frame, row) is covered by the static-box request `classification` sent ahead
-        (`_box_prefetch`; empty on a resumed run that skipped classification, or when the two stages' `valid_only` differ), and every
+        processes (box_mode 'reference', device.moving_boxes 'host': the device mode measures the moving tracks' points with kernel
+        launches), every tracked (frame, row) is covered by the static-box request `classification` sent ahead (`_box_prefetch`; empty on a resumed run that skipped classification, or when the two stages' `valid_only` differ), and every
         tracked frame's points are on the host (`_host_X`) and gathered on the device (`_dev[fnr]['X']`, only handed through).  Anything
         else would launch kernels from the tail thread -- on the thread's default device, with the next sequence's stages running --
         so the caller then runs the tail synchronously on the main thread."""
@@ -422,6 +426,8 @@ class ZeroShotDetector:
             if self.tracker is None or len(self.tracker.tracks_valid) == 0 or self.pipe.box_mode != 'reference' \
                     or self._configured_box_method()[0] != 'minimum_bounding_rectangle':
                 return False
+            if self.moving_boxes == 'device':
+                return False                             # the moving tracks' extents are kernel launches (vg_cluster_oriented_extents)
             tracked = {}
             for t in self.tracker.tracks_valid:
                 for fnr, row in t.source:
@@ -948,21 +954,72 @@ class ZeroShotDetector:
                 for r in range(fs.n_detections):
                     tab.valid[(fs.fnr, r)] = bool(fs.valid[r])
         med = getattr(self, '_med', None) or {}
-        with self._part('boxes.fit_track_boxes'):
+        if self.moving_boxes == 'device':
+            # device.moving_boxes=device: the points of moving tracks are measured where they are (vg_cluster_oriented_extents, one launch
+            # per frame over that frame's (cluster, direction) pairs); no cluster is gathered on the host and no helper process is asked
+            if not med:
+                med = self._tracked_medians(tracked)
+            seg_of = lambda f: self.lidar_frame_list[f].seg_off
+            how = dict(median_of=med.__getitem__, moving_extents=self._moving_extents,
+                       count_of=lambda k: int(seg_of(k[0])[k[1] + 1] - seg_of(k[0])[k[1]]))
+        else:
             # the moving tracks' boxes (per entry: a dozen small numpy calls, ~70 us) are computed by the box helper processes, track
             # by track, while this thread gathers the next track's points; same function, same numpy -> same boxes
             from . import boxes as _boxes
             nproc = self.pipe.box_workers if self.pipe.box_mode == 'reference' else 0
+            how = dict(median_of=(med.__getitem__ if med else None),
+                       moving_async=(lambda p, d, e, c: _boxes.submit_moving_boxes(p, d, e, c, n_procs=nproc)) if nproc > 0 else None,
+                       max_pending=2 * max(nproc, 1))
+        with self._part('boxes.fit_track_boxes'):
             self._host_X3 = {}
             fit_track_boxes(self.tracker, tab, self._cluster_points_host, lambda k: bool(self.lidar_frame_list[k[0]].static[k[1]]),
-                            lambda f: self.lidar_frame_list[f].transform_to_ego, static_box_of=gpu_box.__getitem__,
-                            median_of=(med.__getitem__ if med else None),
-                            moving_async=(lambda p, d, e, c: _boxes.submit_moving_boxes(p, d, e, c, n_procs=nproc)) if nproc > 0 else None,
-                            max_pending=2 * max(nproc, 1))
+                            lambda f: self.lidar_frame_list[f].transform_to_ego, static_box_of=gpu_box.__getitem__, **how)
             self._host_X3 = {}
         self._tab = tab
         with self._part('boxes.write_back'):
             self._write_back_tracked()
+
+    def _tracked_medians(self, tracked):
+        """np.median of every tracked cluster (vg_cluster_medians) when the tracker stage of this run left none: {(fnr, row): [5] f32}."""
+        med, pending = {}, []
+        with self._part('boxes.medians_queue'):
+            for fnr, rows in tracked.items():                # every frame is queued before the first result is read back
+                rows = sorted(rows)
+                X = self._ref_and_nonground(fnr)[1]
+                pending.append((fnr, rows, self.pipe.cluster_medians(X, *self._cluster_lists(fnr, rows))))
+        with self._part('boxes.medians_await'):
+            for fnr, rows, d_med in pending:
+                for r, m in zip(rows, d_med.cpu().numpy()):
+                    med[(fnr, r)] = m
+        return med
+
+    def _moving_extents(self, pairs):
+        """tracking.fit_track_boxes' moving_extents: the oriented extents of all moving tracks' entries.  pairs: (track, entry, key =
+        (fnr, row), rot4, centre).  One upload of the pairs' clusters, centres and rotations, one launch per frame writing its rows of one
+        device buffer, all frames queued before the buffer comes down in one copy."""
+        by_frame = {}
+        for j, (_, _, (fnr, _), _, _) in enumerate(pairs):
+            by_frame.setdefault(fnr, []).append(j)
+        order = np.array([j for js in by_frame.values() for j in js], dtype=np.int64)
+        pipe, dev = self.pipe, self.pipe.device
+        with self._part('boxes.extents_queue'):
+            rows_of = {fnr: sorted({pairs[j][2][1] for j in js}) for fnr, js in by_frame.items()}
+            where = {fnr: {r: i for i, r in enumerate(rows)} for fnr, rows in rows_of.items()}
+            d_pc = torch.from_numpy(np.array([where[pairs[j][2][0]][pairs[j][2][1]] for j in order], dtype=np.int32)).to(dev)
+            d_c3 = torch.from_numpy(np.array([pairs[j][4] for j in order], dtype=np.float32).reshape(-1, 3)).to(dev)
+            d_rot = torch.from_numpy(np.array([pairs[j][3] for j in order], dtype=np.float64).reshape(-1, 4)).to(dev)
+            d_out = torch.empty((len(order), 6), dtype=torch.float64, device=dev)
+            a = 0
+            for fnr, js in by_frame.items():
+                b = a + len(js)
+                X = self._ref_and_nonground(fnr)[1]
+                d_index, d_seg = self._cluster_lists(fnr, rows_of[fnr])
+                pipe.oriented_extents(X, d_index, d_seg, d_pc[a:b], d_c3[a:b], d_rot[a:b], out=d_out[a:b])
+                a = b
+        with self._part('boxes.extents_await'):
+            ext = np.empty((len(order), 6))
+            ext[order] = d_out.cpu().numpy()
+        return ext
 
     def _write_back_tracked(self, key=None):
         tab = self._tab
