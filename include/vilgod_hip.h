@@ -449,6 +449,40 @@ int vg_cluster_ball_count(vg_cluster* h, const float* d_query, int nq, int qstri
 int vg_cluster_nearest(vg_cluster* h, const float* d_query, int nq, int qstride, float max_d2, int32_t* d_idx, float* d_d2,
                        void* stream);
 
+/* ---- K nearest neighbours, no radius limit (csrc/cluster_knn.inc) -------------------------------------------
+ * pytorch3d's `knn_points` as the reference calls it: pointcloud_utils.py:476-493 (chamfer_distance), :496-503 (knn), :505-513
+ * (knn_labels), zero_shot_detector.py:221 (K = 4 among the moving points) and :237 (the label transfer).
+ * The K nearest TARGETS (the set given to the last vg_cluster_grid, or vg_cluster_mst[_nd], on h) of every query row:
+ *   pair distance  float32 d2 = fmaf(dz, dz, fmaf(dy, dy, dx * dx)) on float32 differences -- ONE function (cl_d2_f32), called by the
+ *                  kernel and by vg_knn_host, the one vg_cluster_nearest / vg_cluster_ball_count use
+ *   gate           a target qualifies when d2 <= max_d2; INFINITY: no gate; NaN or <= 0: VG_ERR_ARG (as vg_cluster_nearest)
+ *   order          strict and total: (d2, row in the array given to vg_cluster_grid), ascending.  Row i of d_idx / d_d2 [nq, K] holds
+ *                  the qualifying targets with the K smallest keys in that order.  Equidistant targets compete on the row, whichever
+ *                  cells they lie in and also where K cuts through a group of ties.
+ *   missing        -1 / +inf: fewer than K qualifying targets, an empty grid, and -- in all K places -- a query row with a coordinate
+ *                  that is not finite (decided before any cell arithmetic).  Targets are finite by contract, as for vg_cluster_grid.
+ *   refusals       VG_ERR_ARG for K < 1, K > VG_KNN_MAX_K, qstride < 3, null pointers with nq > 0; nq == 0 is VG_OK.
+ * One launch on `stream`: one lane per query walks the target set's octree depth-first with its K best so far; no atomics, nothing
+ * read back, nothing allocated, capturable.  The order in which nodes are visited decides speed only, never the result.
+ * Where the K best live (the kernel's instantiations; the tests straddle each limit):
+ *   K <= VG_KNN_K_REG1, <= VG_KNN_K_REG4, <= VG_KNN_K_REG8: 1, 4 or 8 register pairs per lane;
+ *   K <= VG_KNN_K_LDS16, <= VG_KNN_MAX_K: a per-lane heap of 16 or 32 entries in LDS. */
+#define VG_KNN_MAX_K 32
+#define VG_KNN_K_REG1 1
+#define VG_KNN_K_REG4 4
+#define VG_KNN_K_REG8 8
+#define VG_KNN_K_LDS16 16
+int vg_cluster_knn(vg_cluster* h, const float* d_query, int nq, int qstride, int K, float max_d2, int32_t* d_idx, float* d_d2,
+                   void* stream);
+/* HOST ONLY, no GPU: the same pair function and the same order over ALL query x target pairs -- no grid, no pruning.
+ * h_target [nt, tstride] (nt = 0: every entry missing); the other arguments and the refusals as above (tstride < 3: VG_ERR_ARG). */
+int vg_knn_host(const float* h_query, int nq, int qstride, const float* h_target, int nt, int tstride, int K, float max_d2,
+                int32_t* h_idx, float* h_d2);
+/* HOST ONLY: the value the kernel compares with a query's K-th best d2 before it skips a node whose box distance
+ * (vg_cluster_geom_probe h_box_d2) is box_d2: a lower bound of the FLOAT32 d2 to every target of the node.  The walk skips the node
+ * only when this value is strictly greater. */
+double vg_knn_prune_bound_host(double box_d2);
+
 /* HOST ONLY, no GPU (like vg_hdbscan_tree_host): the geometry vg_cluster_mst[_nd] prunes with, evaluated on the CPU by the very
  * functions its kernels call, so that the bounds can be checked without a device.  Pair i = (point i, query i), finite float32.
  *   h_origin_in [3] f64 or NULL: the grid's origin; NULL: the origin the kernels derive from the float32 extremes h_bbox_lo/hi [3]

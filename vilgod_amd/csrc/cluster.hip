@@ -19,6 +19,8 @@
 //                         edges are ordered by the STRICT total order
 //                         (w2, pair d2, min id, max id) so the tree is unique and equals the oracle's
 //        radix sort of the n - 1 edges by weight
+// Beside the clustering, on the same grid and tree over a TARGET set (vg_cluster_grid): the fixed-radius queries k_cl_ball_count /
+// k_cl_nearest, and the K nearest targets without a radius, k_cl_knn (cluster_knn.inc).
 // The hierarchy stage (K2d) takes the sorted edges from here: csrc/hdbscan_device.hip on the device, csrc/hdbscan_tree.cpp on the host.
 // The development build adds dev/cluster_dev.inc: the per-point k-NN walk the cooperative phases replaced, and the A/B switches.
 //
@@ -1248,7 +1250,7 @@ __global__ void k_cl_gather_edges(int m, const int* __restrict__ idx_s, const in
 // Fixed-radius queries against the grid of a TARGET point set (entropy scores / two-frame clustering).
 // float32 arithmetic in the order the reference's CUDA ops compile to under nvcc's default FMA contraction:
 //   d2 = fma(dz, dz, fma(dy, dy, dx * dx))      (pcdet ball_query_kernel_stack; pytorch3d KNearestNeighbor dist += diff*diff)
-__device__ __forceinline__ float cl_d2_f32(float qx, float qy, float qz, const float4& b) {
+__host__ __device__ __forceinline__ float cl_d2_f32(float qx, float qy, float qz, const float4& b) {
     const float dx = qx - b.x, dy = qy - b.y, dz = qz - b.z;
     return fmaf(dz, dz, fmaf(dy, dy, dx * dx));
 }
@@ -1331,6 +1333,8 @@ __global__ __launch_bounds__(256) void k_cl_nearest(const float* __restrict__ q,
     idx[i] = bi;
     d2out[i] = best;
 }
+
+#include "cluster_knn.inc"      // K nearest targets, no radius limit: k_cl_knn, vg_cluster_knn, vg_knn_host
 
 // ---------------------------------------------------------------------------------------------
 struct MinOp {

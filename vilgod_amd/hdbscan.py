@@ -104,6 +104,22 @@ class HDBSCAN:
                                      stream_ptr(stream)), 'vg_cluster_nearest')
         return idx, d2
 
+    def knn(self, Q, K, max_d2=float('inf'), out=None, stream=None):
+        """-> (idx int32 [nq,K] rows of the grid's point array, d2 float32 [nq,K]): per query row of Q (CUDA float32 [nq,>=3]) the K
+        grid points with the smallest (float32 d2, row) among those with d2 <= max_d2, in that order; -1 / +inf where there are fewer,
+        and in a whole row whose query is not finite (vg_cluster_knn: no radius limit, one launch).  out: an (idx, d2) pair to write."""
+        assert Q.is_cuda and Q.dtype == torch.float32 and (Q.shape[0] == 0 or Q.stride(1) == 1)
+        nq, K = Q.shape[0], int(K)
+        if out is None:
+            out = (torch.empty((nq, max(K, 0)), dtype=torch.int32, device=Q.device),
+                   torch.empty((nq, max(K, 0)), dtype=torch.float32, device=Q.device))
+        idx, d2 = out
+        assert idx.dtype == torch.int32 and d2.dtype == torch.float32 and idx.shape == d2.shape == (nq, K)
+        assert idx.is_contiguous() and d2.is_contiguous() and idx.device == d2.device == Q.device
+        check(lib.vg_cluster_knn(self._h, ptr(Q), nq, Q.stride(0) if nq else 3, K, float(np.float32(max_d2)), ptr(idx), ptr(d2),
+                                 stream_ptr(stream)), 'vg_cluster_knn')
+        return idx, d2
+
     # ---- GPU stage ---------------------------------------------------------------------------------
     def mst(self, X, want_core=False, stream=None, dim=3):
         """X: CUDA float32 [n,>=dim]; the first `dim` (3..5) columns are the clustering space.
