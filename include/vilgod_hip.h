@@ -246,7 +246,9 @@ int vg_text_encode(vg_text* t, const int32_t* d_tokens, const int32_t* d_eot, in
  * (~150 kernel launches become one graph launch).  A cache belongs to ONE worker: one stream and one set of persistent buffers
  * (every pointer is part of the key).  The data-dependent stages of a frame (ground, clustering, rendering: their launch
  * dimensions change with every frame, and the hierarchy is built on the host) stay plain stream launches around the graph.
- * `stream` must be a created stream (not NULL).  While vg_vit_profile is on, the call falls back to plain launches. */
+ * `stream` must be a created stream (not NULL).  While vg_vit_profile is on, the call falls back to plain launches.  A handle's first
+ * call of every launch form (stream form of the plan, class-row last block, input kind, up to / above 64 classes) runs as plain
+ * launches and counts in no statistic: it sets the kernels' launch attributes, which a capture must not. */
 typedef struct vg_graph_cache vg_graph_cache;
 int vg_graph_cache_create(vg_graph_cache** out);
 void vg_graph_cache_destroy(vg_graph_cache* c);

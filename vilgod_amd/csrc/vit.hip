@@ -169,7 +169,9 @@ struct vg_vit : VitTower {
     // The fp32 originals of in_proj / c_fc stay on the device (w32) so that the folded LayerNorm's pre-scaled fp16 weights are rounded
     // once, from g[k] * W[n,k]; the derived tensors live in `w` under "<name>#ln" (weights), "#c1", "#c2" and are rebuilt when any of
     // their inputs is set again.
-    std::atomic<bool> fold_ready{false}, warmed{false};
+    std::atomic<bool> fold_ready{false};
+    // vg_vit_classify_graph: one bit per launch form (classify_warm_slot, vit_graph.inc) that has run once as plain launches on this handle
+    std::atomic<uint64_t> warmed[2] = {{0}, {0}};
     // single-channel patch rows (vg_vit_encode input_kind 3): per-channel input normalisation the fold assumes (clip.py:79-86; set by
     // vg_vit_set_input_norm) and the readiness of "conv1.weight#1ch" / "positional_embedding#1ch" (vit_fold_conv1)
     float in_mean[3] = {0.48145466f, 0.4578275f, 0.40821073f}, in_std[3] = {0.26862954f, 0.26130258f, 0.27577711f};

@@ -10,6 +10,26 @@ static int classify_scores(const float* d_feat, int n, int dim, const float* d_t
                            : vg_clip_scores_wide(d_feat, n, dim, d_text, n_classes, d_probs, d_top1, d_top1_score, stream);
 }
 
+// The launch form of one classification: everything that selects kernel INSTANTIATIONS in vg_vit_encode + classify_scores beyond what is
+// fixed per handle (type, width, token count, switches) -- the stream form (fp32 / folded fp32 / fp16 pair / fp16: the GEMM epilogues), the
+// last block on the class rows (gather / scatter kernels, the class-row attention), the input kind (im2col instantiation or none, the
+// K of the patch embedding and with it its GEMM family), the narrow or wide scores kernel -- as bit `*bit` of word `*slot` of
+// vg_vit::warmed.  Slot 1: a crop count at which a residual GEMM of the k_gemm_f16_pp64 family runs a split-K tail (VG_GEMM_SPLITK,
+// opt-in), which launches two more kernels.
+static int classify_warm_slot(const vg_vit* v, int n_crops, int input_kind, int n_classes, int* slot, uint64_t* bit) {
+    VitPlan p;
+    const int rc = vit_plan(v, n_crops, input_kind, &p);
+    if (rc) return rc;
+    bool split = false;
+    if (v->dtype == 1 && v->width % 256 == 0 && (p.stream == Stream::F32 || p.stream == Stream::F32_FOLD))
+        for (const int K : {v->width, 4 * v->width})
+            if (!(v->gemm.gemm_w4 && K / 64 >= 4))
+                split = split || splitk_plan((int)(p.Mp / 256), v->width / 256, K / 64, (size_t)p.pe_bytes, v->gemm.splitk_max, vg_cu_count()).parts != 0;
+    *slot = split ? 1 : 0;
+    *bit = 1ull << ((int)p.stream | (p.cls_only_last ? 4 : 0) | (input_kind << 3) | (n_classes > 64 ? 32 : 0));
+    return VG_OK;
+}
+
 /* ---- captured classification (SURVEY 7 step 7 / BASELINE config 5: hipGraph-captured loop) -----------------------------------
  * The launch-heavy, shape-stable part of a frame -- the ~150 kernels of vg_vit_encode + vg_clip_scores -- as ONE hipGraph per
  * distinct crop count, captured on first use and replayed afterwards.  The cache belongs to one worker (one stream, one set of
@@ -63,10 +83,17 @@ int vg_graph_cache_stats(const vg_graph_cache* c, int64_t* h_captured, int64_t* 
 int vg_vit_classify_graph(vg_vit* v, vg_graph_cache* c, const void* d_crops, int input_kind, int n_crops, void* d_workspace, float* d_feat,
                           const float* d_text, int dim, int n_classes, float* d_probs, int32_t* d_top1, float* d_top1_score, void* stream) {
     if (!v || !c || n_crops <= 0 || !stream) return VG_ERR_ARG;          // capture needs a real (non-default) stream
-    // the first encode of a process runs as plain launches: it sets the kernels' dynamic-LDS attributes (hipFuncSetAttribute), which
-    // must not happen inside a capture
-    // (per handle, and the other threads wait for it: it also builds the handle's derived tensors, vit_fold_ln / vit_fold_conv1)
-    const auto cold = [&]() { return !v->warmed.load() || (v->ln_fold && !v->fold_ready.load()) || (input_kind == 3 && !v->conv1_ready.load()); };
+    // Nothing may call hipFuncSetAttribute inside a capture, and the kernels' dynamic-LDS attributes are set lazily, once per kernel
+    // INSTANTIATION, at its first launch (VG_MAX_DYNAMIC_LDS).  Which instantiations a classification launches is decided by its launch
+    // form (classify_warm_slot): a handle's first call of every form runs as plain launches, so a capture only ever launches kernels
+    // that a plain launch of the same handle has launched before.  Guaranteed: no attribute is set inside a capture.  (One plain call
+    // per form and handle, not per crop count: the production buckets of 8 crops and more all share one form.)
+    // The plain call also builds the handle's derived tensors (vit_fold_ln / vit_fold_conv1: they allocate and synchronise); the other
+    // threads wait for it.
+    int slot = 0;
+    uint64_t bit = 0;
+    { const int rc = classify_warm_slot(v, n_crops, input_kind, n_classes, &slot, &bit); if (rc) return rc; }
+    const auto cold = [&]() { return !(v->warmed[slot].load() & bit) || (v->ln_fold && !v->fold_ready.load()) || (input_kind == 3 && !v->conv1_ready.load()); };
     if (cold()) {
         static std::mutex warm_mtx;
         std::lock_guard<std::mutex> lock(warm_mtx);
@@ -74,7 +101,7 @@ int vg_vit_classify_graph(vg_vit* v, vg_graph_cache* c, const void* d_crops, int
             int rc = vg_vit_encode(v, d_crops, input_kind, n_crops, d_workspace, d_feat, stream);
             if (!rc) rc = classify_scores(d_feat, n_crops, dim, d_text, n_classes, d_probs, d_top1, d_top1_score, stream);
             if (!rc) VG_CHECK(hipStreamSynchronize((hipStream_t)stream));
-            v->warmed.store(true);
+            if (!rc) v->warmed[slot].fetch_or(bit);
             return rc;
         }
     }
