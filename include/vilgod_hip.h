@@ -649,6 +649,51 @@ int vg_boxes_iou3d(int dtype, const void* d_a, const int32_t* d_a_off, const voi
 int vg_boxes_iou3d_host(int dtype, const void* h_a, const int32_t* h_a_off, const void* h_b, const int32_t* h_b_off,
                         int n_groups, const int64_t* h_out_off, int mode, double* h_out);
 
+/* Rotated-box NMS: pcdet's iou3d_nms_utils.nms_gpu / nms_normal_gpu, the two functions of the module the reference imports
+ * (src/utils/tracking_utils.py:6, src/vilgod/zero_shot_detector.py:17, src/datasets/waymo_dataset.py:3) next to the IoU above.
+ * Grouped: one call runs n_groups independent NMS passes; group g is the rows [off[g], off[g+1]) of d_boxes / d_scores (off:
+ * n_groups + 1 entries, non-decreasing, inside [0, n_rows]).  Boxes are rows of 7 values {x, y, z, dx, dy, dz, heading}, float32
+ * (VG_NMS_F32, widened exactly) or float64 (VG_NMS_F64); z and dz are not read.  Scores: float32 or float64.  Per group:
+ *   order      rows are ranked by the strict total order (score descending, row index ascending); +0.0 and -0.0 are one score; a NaN
+ *              score ranks behind every number
+ *   padding    a row whose score is NaN, or one of whose x, y, dx, dy, heading is not finite, is never kept and suppresses nothing
+ *              (it keeps its rank).  The rule is this project's own, in both modes
+ *   pre_max    > 0: only the first pre_max ranked rows of each group take part (pcdet's pre_maxsize), the others are not kept;
+ *              <= 0: all take part
+ *   greedy     walking the ranked rows, a row q is kept iff no earlier-KEPT row p has v(q, p) > thresh: strict, and a NaN value
+ *              compares false (|heading| >= 1.6e6 gives one).  v(q, p) is the mode's value with a = row q (the later one) and
+ *              b = row p (the kept one): the geometry is formed in b's frame and is not bit-symmetric, so the operand order is
+ *              part of the contract
+ *   mode VG_NMS_ROTATED   v = the VG_IOU_BEV value of vg_boxes_iou3d (csrc/iou_pair.inc), as in nms_gpu
+ *        VG_NMS_NORMAL    v = the axis-aligned BEV IoU with the headings ignored, as in nms_normal_gpu (csrc/nms_pair.inc): float64,
+ *                         relative to b's centre, d = centre_a - centre_b, ix = min(d.x + ahx, bhx) - max(d.x - ahx, -bhx), iy alike;
+ *                         exactly 0.0 for an extent <= 0, an overlap <= 0 on either axis or a union <= 0, else inter / (Sa + Sb - inter)
+ * Outputs: d_keep int32, one slot per input row: the kept rows of group g as GLOBAL row indices, best first, at
+ * off[g] .. off[g] + count[g] - 1, the rest of the group's slots -1; slots that belong to no group are never written.
+ * d_count int32 [n_groups].
+ * vg_boxes_nms: device pointers, three launches on `stream` (csrc/nms.hip: counting rank, ballot mask over the upper triangle, one
+ * wave per group for the greedy pass), sized from n_groups, n_rows and max_group alone: no read-back, no synchronisation, no
+ * allocation, no atomics -- it can be captured into a graph and gives the same bits on every run.  max_group is the caller's upper
+ * bound on any group's size, at most VG_NMS_MAX_GROUP.  A group the table describes wrongly (larger than max_group, reaching outside
+ * [0, n_rows], negative size) does not fault: its count is -1 and those of its rows that exist get -1, written by the kernels.
+ * d_work: vg_boxes_nms_work_bytes(n_rows, max_group, n_groups) bytes (the ranks and the mask: n_rows * (4 + 8 * ceil(max_group / 64))
+ * rounded up to 8), contents irrelevant before and after; one call at a time per work buffer.
+ * vg_boxes_nms_host: the same arguments over host arrays, no work buffer, the same per-pair and per-row code; the two agree bit
+ * for bit (identical keep lists and counts).  No GPU needed.
+ * VG_ERR_ARG (nothing launched): dtype or mode unknown, a negative n_groups / n_rows / max_group, max_group > VG_NMS_MAX_GROUP, null
+ * pointers with non-empty work.  n_groups == 0 or n_rows == 0: VG_OK, nothing launched, nothing written. */
+#define VG_NMS_F32 0
+#define VG_NMS_F64 1
+#define VG_NMS_ROTATED 0
+#define VG_NMS_NORMAL 1
+#define VG_NMS_MAX_GROUP 4096
+int vg_boxes_nms(int box_dtype, const void* d_boxes, int score_dtype, const void* d_scores, const int32_t* d_off, int n_groups,
+                 int n_rows, int max_group, int mode, double thresh, int pre_max, void* d_work, int32_t* d_keep, int32_t* d_count,
+                 void* stream);
+size_t vg_boxes_nms_work_bytes(int n_rows, int max_group, int n_groups);
+int vg_boxes_nms_host(int box_dtype, const void* h_boxes, int score_dtype, const void* h_scores, const int32_t* h_off, int n_groups,
+                      int n_rows, int max_group, int mode, double thresh, int pre_max, int32_t* h_keep, int32_t* h_count);
+
 /* Points in boxes: pcdet's roiaware_pool3d_utils.points_in_boxes_gpu, which the reference calls in src/utils/pointcloud_utils.py:144-158
  * (get_box_heights) and :516-522 (points_in_boxes; src/vilgod/lidar_frame.py:154-161 turns box proposals into detections with it).
  * Per point the LOWEST index of a box that contains it, -1 when none does.  A box is a row of 7 values {cx, cy, cz, dx, dy, dz, rz},

@@ -35,6 +35,7 @@ SOURCES = {
     'segment.hip': ['-ffp-contract=off'],
     'lshape.hip': ['-ffp-contract=off'],
     'iou.hip': ['-ffp-contract=off'],
+    'nms.hip': ['-ffp-contract=off'],
     'points_in_boxes.hip': ['-ffp-contract=off'],
     'oriented_extent.hip': ['-ffp-contract=off'],
     'pack.hip': [],

@@ -1023,7 +1023,7 @@ class PseudoLabelPipeline:
         fs.set_classes(key, which, names[mapped], fine_names[fine], sc, names[win], final)
         return names, win, final
 
-    def label_proposals(self, points, pose, ref_pose, proposals, names=None, fnr=0, state=None):
+    def label_proposals(self, points, pose, ref_pose, proposals, names=None, fnr=0, state=None, scores=None, nms=None):
         """Zero-shot labels for box proposals: LidarFrame.generate_detections(None, proposals=..., names=...) (lidar_frame.py:154-161,
         244-247) followed by the classification and the vote.  proposals: [P, >=7] boxes [x, y, z, dx, dy, dz, heading] in the EGO frame
         (a detector's, another pipeline's, annotations); names: P entries kept as object_class['proposal'].
@@ -1032,7 +1032,14 @@ class PseudoLabelPipeline:
         `self.pack`, FrameState.set_proposals, `classify` on the full point table, `vote_classes`.  No filter runs: every proposal that
         owns a point is classified; the others are absent from the frame state and from the result.
         -> (FrameState, result dict as `label`'s: boxes_lidar are the INPUT boxes of the kept rows, not refitted; moving all False;
-        restricted to class_names).  `proposal_rows(fs)` gives the proposal index of each result row."""
+        restricted to class_names).  `proposal_rows(fs)` gives the proposal index of each result row.
+        vg_points_in_boxes gives a point to the LOWEST-index proposal that contains it, so a duplicate proposal steals the points of
+        the box it duplicates or owns none and drops out.  nms={'thresh': t, 'mode': 'rotated' | 'normal', 'pre_maxsize': None} with
+        `scores` (P entries) runs ONE nms.nms_groups call over the ego-frame proposals first (pcdet's nms_gpu / nms_normal_gpu rules:
+        best score first, a proposal goes when its BEV IoU with a kept one is > t).  The survivors go on in their ORIGINAL relative
+        order, `names` cut alike, so the lowest-index rule means what it meant; the frame state is that of the surviving list (its
+        cluster_ids count inside it, fs.proposal_index maps them back) and `proposal_rows(fs)` keeps returning indices into the
+        caller's ORIGINAL list.  nms=None (the default) changes nothing; `scores` alone is not used."""
         from .points_in_boxes import points_in_boxes_gpu
         from .sequence_datasets import apply_transform
         proposals = np.asarray(proposals)
@@ -1043,7 +1050,16 @@ class PseudoLabelPipeline:
         P = len(proposals)
         if names is not None and len(names) != P:
             raise ValueError(f'names: {len(names)} entries for {P} proposals')
+        if nms is not None:
+            from . import nms as box_nms
+            if not isinstance(nms, dict) or 'thresh' not in nms or set(nms) - {'thresh', 'mode', 'pre_maxsize'}:
+                raise ValueError(f"nms: None or a dict with 'thresh' and optionally 'mode', 'pre_maxsize', got {nms!r}")
+            box_nms._mode(nms.get('mode', 'rotated'))
+            box_nms._pre_max(nms.get('pre_maxsize'))
+            if scores is None or np.shape(scores) != (P,):
+                raise ValueError(f'scores: nms needs one score per proposal ({P}), got {None if scores is None else np.shape(scores)}')
         fs = state if state is not None else FrameState(fnr, pose, ref_pose)
+        fs.proposal_index = None                         # (a state handed in may carry an earlier call's)
         self.last_probs = torch.zeros((0, len(self.class_list)), dtype=torch.float32, device=self.device)
         result = {'boxes_lidar': np.zeros((0, 7)), 'name': np.array([]), 'score': np.array([]), 'moving': np.array([])}
         d_pts = self.upload(points)
@@ -1052,6 +1068,20 @@ class PseudoLabelPipeline:
         if P == 0 or n == 0:
             fs.set_proposals(np.zeros((0, 7)) if P == 0 else proposals_ref, np.full(n, -1, np.int64), None if P == 0 else names)
             return fs, result
+        if nms is not None:
+            d_prop = torch.from_numpy(np.ascontiguousarray(proposals[:, :7], dtype=np.float32 if proposals.dtype == np.float32 else np.float64))
+            sc = np.asarray(scores)
+            d_sc = torch.from_numpy(np.ascontiguousarray(sc, dtype=np.float32 if sc.dtype == np.float32 else np.float64))
+            keep, count = box_nms.nms_groups(d_prop.to(self.device), d_sc.to(self.device), [0, P], nms['thresh'], nms.get('mode', 'rotated'),
+                                             nms.get('pre_maxsize'))
+            sel = np.sort(keep[:int(count[0])].cpu().numpy()).astype(np.int64)           # the survivors in their original relative order
+            proposals, proposals_ref = proposals[sel], proposals_ref[sel]
+            names = None if names is None else [names[i] for i in sel]
+            fs.proposal_index = sel
+            P = len(sel)
+            if P == 0:
+                fs.set_proposals(np.zeros((0, 7)), np.full(n, -1, np.int64), None)
+                return fs, result
         d_ref = self.to_ref(d_pts, fs.transform_to_ref)
         d_boxes = torch.from_numpy(np.ascontiguousarray(proposals_ref[:, :7], dtype=np.float32)).to(self.device)
         d_labels = points_in_boxes_gpu(d_ref.unsqueeze(0), d_boxes.unsqueeze(0))[0]
@@ -1082,7 +1112,8 @@ class PseudoLabelPipeline:
         if e is None:
             return np.zeros(0, np.int64)
         keep = np.array([bool(h) and nm in self.class_names for h, nm in zip(e['has'], e['name'])], dtype=bool)
-        return fs.cluster_ids[keep]
+        rows, sel = fs.cluster_ids[keep], getattr(fs, 'proposal_index', None)              # (label_proposals' nms: the surviving list)
+        return rows if sel is None else sel[rows]
 
     def label(self, fs, d_ref, d_X, gidx, labels, probs, entropy=None, t=None, t0=None, tick=None, before_classify=None):
         """Everything after clustering: detections, static flags, filters, classification, boxes, results."""
