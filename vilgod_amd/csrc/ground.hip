@@ -7,11 +7,13 @@
 //                   binning (:579-623) -> patch id; LDS-privatised histogram of patch sizes
 //   k_pw_offsets    504-entry exclusive scan
 //   k_pw_scatter    (z-key, index) 64-bit keys grouped by patch
+//   k_pw_sort_big   the keys of the few patches above 4096 points, sorted in one CU's LDS
 //   k_pw_patch      ONE WORKGROUP PER PATCH: bitonic sort of the keys in LDS (= std::sort by z, :200,
 //                   ties by index), then R-VPF / R-GPF (:468-550) as predicate-masked block reductions
-//                   over the sorted points held in LDS, 3x3 eigen-solve per thread
-//   k_pw_decide     one lane per ring: GLE decision tree (:218-283), TGR (:403-465); then the adaptive
-//                   threshold update (:339-376) with the per-sequence state kept in HBM
+//                   over the sorted points, 3x3 eigen-solve per thread: one body (pw_patch_body) over a patch
+//                   held in LDS (PwLdsPatch) or, above 4096 points, read from global memory (PwGlobalPatch)
+//   k_pw_decide     one lane per ring: GLE decision tree (:218-283), then TGR (:403-465); then the adaptive
+//                   threshold update (:339-376) over the eight stores (PwStore) of the per-sequence state in HBM
 //   k_pw_finalize   per point: ground = in its patch's plane inliers AND patch accepted
 //
 // Numeric model (identical to oracle/patchworkpp_oracle.cpp, see DESIGN.md "ground numerics"): float64 sums
@@ -22,6 +24,8 @@
 #include <float.h>
 #include <math.h>
 #include <string.h>
+#include <memory>
+#include <vector>
 
 #define PW_MAX_PATCHES 1024
 #define PW_STORE_CAP 2048            // ring buffers for update_elevation_/update_flatness_ (1000 + <=54 per frame)
@@ -31,16 +35,19 @@
 
 struct PwGeom {                      // derived in the constructor, patchworkpp.h:116-131
     double min_ranges[4], ring_sizes[4], sector_sizes[4];
-    int patch_base[5];
-    int n_patches;
+    int patch_base[5], ring_base[5]; // first patch / first ring (concentric index) of each zone; [4] = the totals
+    int n_patches, n_rings;
 };
 
-struct PwState {                     // everything Patchwork++ carries from frame to frame
+struct PwStateHead {
     double sensor_height;
     double elevation_thr[4], flatness_thr[4];
     int elev_head[4], elev_cnt[4], flat_head[4], flat_cnt[4];
+};
+struct PwState : PwStateHead {       // everything Patchwork++ carries from frame to frame; its bytes are the blob that handles hand each other
     double elev[4][PW_STORE_CAP], flat[4][PW_STORE_CAP];
 };
+static_assert(sizeof(PwStateHead) == 136 && sizeof(PwState) == 136 + 8 * 8 * PW_STORE_CAP, "the state blob's layout is fixed");
 
 struct PwPatchRec {
     int n, n_ground;
@@ -49,11 +56,9 @@ struct PwPatchRec {
 };
 
 struct vg_ground {
-    vg_ground_params p;
+    vg_ground_params p;     // p and g go to the kernels by value: vg_ground_estimate reads them when it enqueues
     PwGeom g;
     int max_points;
-    vg_ground_params* d_p;
-    PwGeom* d_g;
     PwState* d_state;
     int* d_patch_id;        // [max_points]
     int* d_count;           // [PW_MAX_PATCHES] sizes, then cursors
@@ -66,9 +71,8 @@ struct vg_ground {
 
 // ---------------------------------------------------------------------------------------------
 __global__ void k_pw_classify(const float* __restrict__ pts, int n, int stride, double z_offset,
-                              const vg_ground_params* __restrict__ P, const PwGeom* __restrict__ G,
-                              const PwState* __restrict__ S, int* __restrict__ patch_id, int* __restrict__ count,
-                              unsigned char* __restrict__ inlier) {
+                              const vg_ground_params P, const PwGeom G, const PwState* __restrict__ S,
+                              int* __restrict__ patch_id, int* __restrict__ count, unsigned char* __restrict__ inlier) {
     __shared__ int hist[PW_MAX_PATCHES];
     for (int b = threadIdx.x; b < PW_MAX_PATCHES; b += blockDim.x) hist[b] = 0;
     __syncthreads();
@@ -81,25 +85,25 @@ __global__ void k_pw_classify(const float* __restrict__ pts, int n, int stride, 
         const float inten = pts[(size_t)i * stride + 3];
         int pid = -1;
         bool noise = false;
-        if (P->enable_RNR) {
+        if (P.enable_RNR) {
             float rr = x * x + y * y;
             // patchworkpp.cpp:388: `sqrt` of a FLOAT expression under `using namespace std` (patchworkpp.h:10) is the float
             // overload; (float)sqrt((double)rr) is that correctly rounded float root (53 >= 2*24+2 bits: no double rounding)
             double r = (double)(float)sqrt((double)rr);
             double zd = z;
             double ang = atan2(zd, r) * 180 / M_PI;
-            noise = ang < P->RNR_ver_angle_thr && zd < -S->sensor_height - 0.8 && (double)inten < P->RNR_intensity_thr;
+            noise = ang < P.RNR_ver_angle_thr && zd < -S->sensor_height - 0.8 && (double)inten < P.RNR_intensity_thr;
         }
         if (!noise && z != FLT_MIN) {
             double xd = x, yd = y;
             double r = sqrt(xd * xd + yd * yd);
-            if (r <= P->max_range && r > P->min_range) {
+            if (r <= P.max_range && r > P.min_range) {
                 double theta = atan2(yd, xd);
                 if (!(theta > 0)) theta = 2 * M_PI + theta;
-                int zone = r < G->min_ranges[1] ? 0 : (r < G->min_ranges[2] ? 1 : (r < G->min_ranges[3] ? 2 : 3));
-                int ring = min((int)((r - G->min_ranges[zone]) / G->ring_sizes[zone]), P->num_rings_each_zone[zone] - 1);
-                int sector = min((int)(theta / G->sector_sizes[zone]), P->num_sectors_each_zone[zone] - 1);
-                pid = G->patch_base[zone] + ring * P->num_sectors_each_zone[zone] + sector;
+                int zone = r < G.min_ranges[1] ? 0 : (r < G.min_ranges[2] ? 1 : (r < G.min_ranges[3] ? 2 : 3));
+                int ring = min((int)((r - G.min_ranges[zone]) / G.ring_sizes[zone]), P.num_rings_each_zone[zone] - 1);
+                int sector = min((int)(theta / G.sector_sizes[zone]), P.num_sectors_each_zone[zone] - 1);
+                pid = G.patch_base[zone] + ring * P.num_sectors_each_zone[zone] + sector;
             }
         }
         patch_id[i] = pid;
@@ -301,63 +305,77 @@ __device__ void pw_bitonic_sort(KP keys, int n) {
     }
 }
 
-template <bool BIG>
-__device__ void pw_patch_body(const float* __restrict__ pts, int stride, const vg_ground_params* __restrict__ P,
-                              const PwState* __restrict__ S, int zone, int n, unsigned long long* gkeys,
-                              unsigned char* __restrict__ inlier, PwPatchRec& rec, unsigned long long* lkeys,
-                              float* lx, float* ly, unsigned char* lalive, double* red, double* bc) {
-    const int tid = threadIdx.x;
-    // ---- sort by (z, index) ----
-    if (!BIG) {
-        for (int i = tid; i < n; i += PW_T) lkeys[i] = gkeys[i];
-        __syncthreads();
-        pw_bitonic_sort(lkeys, n);
-        for (int i = tid; i < n; i += PW_T) {
-            unsigned int idx = (unsigned int)(lkeys[i] & 0xFFFFFFFFull);
-            lx[i] = pts[(size_t)idx * stride];
-            ly[i] = pts[(size_t)idx * stride + 1];
-            lalive[i] = 1;
-        }
-    } else {
-        if (n > PW_BIG_LDS_POINTS) pw_bitonic_sort(gkeys, n);      // up to PW_BIG_LDS_POINTS k_pw_sort_big has sorted the keys already
-        __threadfence_block();
-        // alive flags of big patches live in the inlier array (indexed by ORIGINAL point index): 2 = alive
-        for (int i = tid; i < n; i += PW_T) inlier[(unsigned int)(gkeys[i] & 0xFFFFFFFFull)] = 2;
-    }
-    __syncthreads();
-#define PW_KEY(i) (BIG ? gkeys[i] : lkeys[i])
-#define PW_IDX(i) ((unsigned int)(PW_KEY(i) & 0xFFFFFFFFull))
-#define PW_Z(i) vg_fkey_inv((uint32_t)(PW_KEY(i) >> 32))
-#define PW_X(i) (BIG ? pts[(size_t)PW_IDX(i) * stride] : lx[i])
-#define PW_Y(i) (BIG ? pts[(size_t)PW_IDX(i) * stride + 1] : ly[i])
-#define PW_ALIVE(i) (BIG ? (inlier[PW_IDX(i)] == 2) : (lalive[i] != 0))
-#define PW_KILL(i)                      \
-    do {                                \
-        if (BIG) inlier[PW_IDX(i)] = 0; \
-        else lalive[i] = 0;             \
-    } while (0)
+// A patch as pw_patch_body sees it: its n points in (z, index) order, point i's index in the scan, coordinates and alive flag
+// (R-VPF removes points).  Two storages behind the same members; both are built in k_pw_patch from its own arrays and arguments, so
+// that the compiler still sees which pointer is LDS and which is global memory (hdbscan_device.hip: what a flat access to LDS costs).
+struct PwSortedKeys {                // k_pw_scatter's keys: (order-preserving key of the offset z) << 32 | index in the scan
+    unsigned long long* keys;
+    __device__ unsigned int idx(int i) const { return (unsigned int)(keys[i] & 0xFFFFFFFFull); }
+    __device__ float z(int i) const { return vg_fkey_inv((uint32_t)(keys[i] >> 32)); }
+};
 
-    PwPlane pl;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) pl.normal[i] = pl.mean[i] = pl.sv[i] = 0.f;
-    pl.d = 0.0;
-    const double sensor_height = S->sensor_height;
+struct PwLdsPatch : PwSortedKeys {   // n <= PW_LDS_POINTS: keys, x, y and alive bytes in the workgroup's LDS, [PW_LDS_POINTS] each
+    float *xs, *ys;
+    unsigned char* live;
+    const unsigned long long* gkeys; // the patch's keys as k_pw_scatter left them
+    const float* pts;
+    int stride, n;
+    __device__ float x(int i) const { return xs[i]; }
+    __device__ float y(int i) const { return ys[i]; }
+    __device__ bool alive(int i) const { return live[i] != 0; }
+    __device__ void kill(int i) const { live[i] = 0; }
+    __device__ void load() const {   // sort by (z, index), gather x / y once
+        for (int i = threadIdx.x; i < n; i += PW_T) keys[i] = gkeys[i];
+        __syncthreads();
+        pw_bitonic_sort(keys, n);
+        for (int i = threadIdx.x; i < n; i += PW_T) {
+            const unsigned int p = idx(i);
+            xs[i] = pts[(size_t)p * stride];
+            ys[i] = pts[(size_t)p * stride + 1];
+            live[i] = 1;
+        }
+    }
+    __device__ void finish() const {}
+};
+
+struct PwGlobalPatch : PwSortedKeys { // larger patches: sorted keys in global memory, x / y from the point rows
+    const float* pts;
+    unsigned char* inlier;           // alive flags live in the inlier array (indexed by ORIGINAL point index): 2 = alive
+    int stride, n;
+    __device__ float x(int i) const { return pts[(size_t)idx(i) * stride]; }
+    __device__ float y(int i) const { return pts[(size_t)idx(i) * stride + 1]; }
+    __device__ bool alive(int i) const { return inlier[idx(i)] == 2; }
+    __device__ void kill(int i) const { inlier[idx(i)] = 0; }
+    __device__ void load() const {
+        if (n > PW_BIG_LDS_POINTS) pw_bitonic_sort(keys, n);       // up to PW_BIG_LDS_POINTS k_pw_sort_big has sorted the keys already
+        __threadfence_block();
+        for (int i = threadIdx.x; i < n; i += PW_T) inlier[idx(i)] = 2;
+    }
+    __device__ void finish() const { // surviving "alive" marks (2) of non-inliers must not leak into the inlier flags
+        __syncthreads();
+        for (int i = threadIdx.x; i < n; i += PW_T)
+            if (inlier[idx(i)] == 2) inlier[idx(i)] = 0;
+    }
+};
+
+template <class Patch>
+__device__ void pw_patch_body(const Patch& pt, const vg_ground_params& P, double sensor_height, int zone,
+                              unsigned char* __restrict__ inlier, PwPatchRec& rec, double* red, double* bc) {
+    const int tid = threadIdx.x, n = pt.n;
+    pt.load();
+    __syncthreads();
+    PwPlane pl = {};
 
     auto seed_threshold = [&](double th) -> double {   // extract_initial_seeds, :78-150
         __syncthreads();
         if (tid == 0) {
             double sum = 0;
             int cnt = 0, i = 0;
-            if (zone == 0) {
-                for (; i < n; ++i) {
-                    if (!PW_ALIVE(i)) continue;
-                    if ((double)PW_Z(i) < P->adaptive_seed_selection_margin * sensor_height) continue;
-                    break;
-                }
-            }
-            for (; i < n && cnt < P->num_lpr; ++i) {
-                if (!PW_ALIVE(i)) continue;
-                sum += (double)PW_Z(i);
+            if (zone == 0)                                 // skip the points below the margin
+                while (i < n && (!pt.alive(i) || (double)pt.z(i) < P.adaptive_seed_selection_margin * sensor_height)) ++i;
+            for (; i < n && cnt < P.num_lpr; ++i) {
+                if (!pt.alive(i)) continue;
+                sum += (double)pt.z(i);
                 cnt++;
             }
             double lpr = cnt != 0 ? sum / cnt : 0;
@@ -368,21 +386,19 @@ __device__ void pw_patch_body(const float* __restrict__ pts, int stride, const v
     };
     // estimate_plane over {alive, pred}: pred 0: z < thr;  pred 1: signed plane distance < th_dist
     auto fit = [&](int pred, double thr, bool mark_inliers) {
-        double v[9];
-#pragma unroll
-        for (int k = 0; k < 9; ++k) v[k] = 0.0;
+        double v[9] = {};
         int cnt = 0;
         const PwPlane cur = pl;
         for (int i = tid; i < n; i += PW_T) {
-            if (!PW_ALIVE(i)) continue;
-            const float x = PW_X(i), y = PW_Y(i), z = PW_Z(i);
+            if (!pt.alive(i)) continue;
+            const float x = pt.x(i), y = pt.y(i), z = pt.z(i);
             bool take = pred == 0 ? ((double)z < thr) : (pw_plane_dist(cur, x, y, z) < thr);
             if (take) {
                 double X = x, Y = y, Z = z;
                 v[0] += X; v[1] += Y; v[2] += Z;
                 v[3] += X * X; v[4] += X * Y; v[5] += X * Z; v[6] += Y * Y; v[7] += Y * Z; v[8] += Z * Z;
                 cnt++;
-                if (mark_inliers) inlier[PW_IDX(i)] = 1;
+                if (mark_inliers) inlier[pt.idx(i)] = 1;
             }
         }
         double Sm[9];
@@ -393,69 +409,56 @@ __device__ void pw_patch_body(const float* __restrict__ pts, int stride, const v
     };
 
     // ---- R-VPF, :478-509 ----
-    if (P->enable_RVPF) {
-        for (int it = 0; it < P->num_iter; ++it) {
-            double thr = seed_threshold(P->th_seeds_v);
-            fit(0, thr, false);
-            if (zone == 0 && (double)pl.normal[2] < P->uprightness_thr) {
-                for (int i = tid; i < n; i += PW_T)
-                    if (PW_ALIVE(i) && fabs(pw_plane_dist(pl, PW_X(i), PW_Y(i), PW_Z(i))) < P->th_dist_v) PW_KILL(i);
-            } else
-                break;
+    if (P.enable_RVPF) {
+        for (int it = 0; it < P.num_iter; ++it) {
+            fit(0, seed_threshold(P.th_seeds_v), false);
+            if (!(zone == 0 && (double)pl.normal[2] < P.uprightness_thr)) break;
+            for (int i = tid; i < n; i += PW_T)
+                if (pt.alive(i) && fabs(pw_plane_dist(pl, pt.x(i), pt.y(i), pt.z(i))) < P.th_dist_v) pt.kill(i);
         }
     }
     // ---- R-GPF, :511-544 ----
-    {
-        double thr = seed_threshold(P->th_seeds);
-        fit(0, thr, false);
-    }
-    int n_ground = 0;
-    for (int it = 0; it < P->num_iter; ++it) {
+    fit(0, seed_threshold(P.th_seeds), false);
+    for (int it = 0; it < P.num_iter; ++it) {
         __syncthreads();
-        n_ground = fit(1, P->th_dist, it == P->num_iter - 1);
+        rec.n_ground = fit(1, P.th_dist, it == P.num_iter - 1);
     }
-    if (BIG) {   // surviving "alive" marks (2) of non-inliers must not leak into the inlier flags
-        __syncthreads();
-        for (int i = tid; i < n; i += PW_T)
-            if (inlier[PW_IDX(i)] == 2) inlier[PW_IDX(i)] = 0;
-    }
-    rec.n_ground = n_ground;
+    pt.finish();
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
         rec.normal[i] = pl.normal[i];
         rec.mean[i] = pl.mean[i];
         rec.sv[i] = pl.sv[i];
     }
-#undef PW_KEY
-#undef PW_IDX
-#undef PW_Z
-#undef PW_X
-#undef PW_Y
-#undef PW_ALIVE
-#undef PW_KILL
 }
 
 // Patches too large for k_pw_patch's LDS image (a handful of near-range patches per scan: 4 097 ... 9 646 points on the benchmark
 // frames) used to be sorted in global memory by their 256-thread workgroup -- 105 compare-exchange stages over L2 for 9 646 keys,
 // 0.43 ms of a 1.15 ms ground pass.  Their keys alone fit the LDS of one CU: 1024 threads sort them there first (keys are unique, so
 // the order is the same one).
-__global__ __launch_bounds__(1024) void k_pw_sort_big(const vg_ground_params* __restrict__ P, const int* __restrict__ offset,
+__global__ __launch_bounds__(1024) void k_pw_sort_big(int num_min_pts, const int* __restrict__ offset,
                                                       unsigned long long* __restrict__ keys) {
     extern __shared__ unsigned long long pw_sk[];
     const int pid = blockIdx.x;
     const int o = offset[pid], n = offset[pid + 1] - o;
-    if (n <= PW_LDS_POINTS || n > PW_BIG_LDS_POINTS || n < P->num_min_pts) return;      // workgroup-uniform
+    if (n <= PW_LDS_POINTS || n > PW_BIG_LDS_POINTS || n < num_min_pts) return;      // workgroup-uniform
     for (int i = threadIdx.x; i < n; i += blockDim.x) pw_sk[i] = keys[o + i];
     __syncthreads();
     pw_bitonic_sort(pw_sk, n);
     for (int i = threadIdx.x; i < n; i += blockDim.x) keys[o + i] = pw_sk[i];
 }
 
-__global__ __launch_bounds__(PW_T) void k_pw_patch(const float* __restrict__ pts, int stride,
-                                                   const vg_ground_params* __restrict__ P, const PwGeom* __restrict__ G,
-                                                   const PwState* __restrict__ S, const int* __restrict__ offset,
-                                                   unsigned long long* __restrict__ keys, unsigned char* __restrict__ inlier,
-                                                   PwPatchRec* __restrict__ recs) {
+// The zone whose [base[zone], base[zone + 1]) holds v: a patch against PwGeom::patch_base, a ring against ring_base
+__device__ __forceinline__ int pw_zone(const int* base, int v) {
+    int zone = 0;
+    while (zone < 3 && v >= base[zone + 1]) zone++;
+    return zone;
+}
+
+__global__ __launch_bounds__(PW_T) void k_pw_patch(const float* __restrict__ pts, int stride, const vg_ground_params P,
+                                                   const PwGeom G, const PwState* __restrict__ S,
+                                                   const int* __restrict__ offset, unsigned long long* __restrict__ keys,
+                                                   unsigned char* __restrict__ inlier, PwPatchRec* __restrict__ recs) {
     __shared__ unsigned long long lkeys[PW_LDS_POINTS];
     __shared__ float lx[PW_LDS_POINTS], ly[PW_LDS_POINTS];
     __shared__ unsigned char lalive[PW_LDS_POINTS];
@@ -463,152 +466,145 @@ __global__ __launch_bounds__(PW_T) void k_pw_patch(const float* __restrict__ pts
     __shared__ double bc[2];
     const int pid = blockIdx.x;
     const int o = offset[pid], n = offset[pid + 1] - o;
-    PwPatchRec rec;
+    PwPatchRec rec = {};
     rec.n = n;
-    rec.n_ground = 0;
-    rec.decision = 0;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) rec.normal[i] = rec.mean[i] = rec.sv[i] = 0.f;
-    if (n >= P->num_min_pts) {   // :192-196
-        int zone = 0;
-        while (zone < 3 && pid >= G->patch_base[zone + 1]) zone++;
+    if (n >= P.num_min_pts) {    // :192-196
+        const int zone = pw_zone(G.patch_base, pid);
         rec.decision = -1;       // to be decided by k_pw_decide
         if (n <= PW_LDS_POINTS)
-            pw_patch_body<false>(pts, stride, P, S, zone, n, keys + o, inlier, rec, lkeys, lx, ly, lalive, red, bc);
+            pw_patch_body(PwLdsPatch{{lkeys}, lx, ly, lalive, keys + o, pts, stride, n}, P, S->sensor_height, zone, inlier, rec, red, bc);
         else
-            pw_patch_body<true>(pts, stride, P, S, zone, n, keys + o, inlier, rec, lkeys, lx, ly, lalive, red, bc);
+            pw_patch_body(PwGlobalPatch{{keys + o}, pts, inlier, stride, n}, P, S->sensor_height, zone, inlier, rec, red, bc);
     }
     if (threadIdx.x == 0) recs[pid] = rec;
 }
 
 // ---------------------------------------------------------------------------------------------
-// lane r < n_rings: sequential GLE + TGR for ring r (concentric index r).  Then lanes 0..3 / 8..11 update thresholds.  (256 threads:
-// the other three waves only help with the copies into LDS.)
-__global__ __launch_bounds__(256) void k_pw_decide(vg_ground_params* __restrict__ P, const PwGeom* __restrict__ G,
-                                                  PwState* __restrict__ S, PwPatchRec* __restrict__ recs) {
-    const int lane = threadIdx.x;
-    __shared__ double sh_rf[4][64];          // per near ring: the flatness values it appends to `ringwise_flatness`
-    __shared__ int sh_nrf[4], sh_ncand[4];
-    // one 48 KB buffer, two uses: the patch records while the rings are decided (each ring's lane walks its <= 54 sectors one
-    // after the other: from LDS, not through ~100 dependent reads of global memory), then the threshold stores (below)
-    __shared__ double raw[PW_MAX_PATCHES * sizeof(PwPatchRec) / 8];
-    PwPatchRec* const lrec = reinterpret_cast<PwPatchRec*>(raw);
-    if (lane < 4) { sh_nrf[lane] = 0; sh_ncand[lane] = 0; }
-    int n_rings = 0, n_patches = 0;
-    for (int k = 0; k < P->num_zones; ++k) { n_rings += P->num_rings_each_zone[k]; n_patches += P->num_rings_each_zone[k] * P->num_sectors_each_zone[k]; }
-    for (int w = lane; w < n_patches * (int)(sizeof(PwPatchRec) / 4); w += blockDim.x) reinterpret_cast<int*>(raw)[w] = reinterpret_cast<const int*>(recs)[w];
-    __syncthreads();
-    if (lane < n_rings) {
-        int zone = 0, ring = lane;
-        while (ring >= P->num_rings_each_zone[zone]) { ring -= P->num_rings_each_zone[zone]; zone++; }
-        const int cidx = lane;
-        const int ns = P->num_sectors_each_zone[zone];
-        const int base = G->patch_base[zone] + ring * ns;
-        const bool is_near = cidx < P->num_rings_of_interest;
-        double* rf = sh_rf[cidx < 4 ? cidx : 0];    // this ring's part of `ringwise_flatness` (<= sectors per ring <= 64; only near rings add to it)
-        int nrf = 0, ncand = 0;
-        for (int s = 0; s < ns; ++s) {
-            PwPatchRec& r = lrec[base + s];
-            if (r.decision != -1) continue;              // < num_min_pts points: all non-ground
-            const double upright = r.normal[2], elevation = r.mean[2];
-            const double flatness = fmin(fmin((double)r.sv[0], (double)r.sv[1]), (double)r.sv[2]);
-            double heading = 0.0;
-            for (int i = 0; i < 3; ++i) heading += (double)(r.mean[i] * r.normal[i]);
-            const bool is_upright = upright > P->uprightness_thr;
-            const bool heading_outside = heading < 0.0;
-            bool not_elevated = false, is_flat = false;
-            if (is_near) {
-                not_elevated = elevation < S->elevation_thr[cidx];
-                is_flat = flatness < S->flatness_thr[cidx];
-            }
-            if (is_upright && not_elevated && is_near) {     // :254-260
-                int e = (S->elev_head[cidx] + S->elev_cnt[cidx]) & (PW_STORE_CAP - 1);
-                S->elev[cidx][e] = elevation;
-                S->elev_cnt[cidx]++;
-                int f = (S->flat_head[cidx] + S->flat_cnt[cidx]) & (PW_STORE_CAP - 1);
-                S->flat[cidx][f] = flatness;
-                S->flat_cnt[cidx]++;
-                rf[nrf++] = flatness;
-            }
-            int decision;
-            if (!is_upright) decision = 0;
-            else if (!is_near) decision = 1;
-            else if (!heading_outside) decision = 0;
-            else if (not_elevated || is_flat) decision = 1;
-            else { decision = 2; ncand++; }
-            r.decision = decision;
-        }
-        if (cidx < 4) { sh_nrf[cidx] = nrf; sh_ncand[cidx] = ncand; }
+// k_pw_decide's pieces.  A ring is named by its concentric index over all zones; the first num_rings_of_interest (<= 4) are "near".
+struct PwRing { int first_patch, sectors; };
+__device__ __forceinline__ PwRing pw_ring(const vg_ground_params& P, const PwGeom& G, int cidx) {
+    const int zone = pw_zone(G.ring_base, cidx), ns = P.num_sectors_each_zone[zone];
+    return {G.patch_base[zone] + (cidx - G.ring_base[zone]) * ns, ns};
+}
+
+__device__ __forceinline__ double pw_flatness(const PwPatchRec& r) { return fmin(fmin((double)r.sv[0], (double)r.sv[1]), (double)r.sv[2]); }
+
+// One of the eight adaptive stores, a ring buffer over PwState's fields: id 0..3 = the elevations of near ring id, 4..7 = the
+// flatness values of near ring id - 4
+struct PwStore {
+    int *head, *cnt;
+    double* v;                       // [PW_STORE_CAP]
+    __device__ PwStore(PwState* S, int id)
+        : head(id < 4 ? &S->elev_head[id] : &S->flat_head[id - 4]), cnt(id < 4 ? &S->elev_cnt[id] : &S->flat_cnt[id - 4]),
+          v(id < 4 ? S->elev[id] : S->flat[id - 4]) {}
+    __device__ void push(double x) const {
+        v[(*head + *cnt) & (PW_STORE_CAP - 1)] = x;
+        ++*cnt;
     }
-    __syncthreads();
-    if (lane < n_rings) {
-        int zone = 0, ring = lane;
-        while (ring >= P->num_rings_each_zone[zone]) { ring -= P->num_rings_each_zone[zone]; zone++; }
-        const int cidx = lane;
-        const int ns = P->num_sectors_each_zone[zone];
-        const int base = G->patch_base[zone] + ring * ns;
-        const int ncand = cidx < 4 ? sh_ncand[cidx] : 0;
-        if (ncand > 0) {                                     // :293-305
-            // `ringwise_flatness` is cleared only at the end of a ring that HAD candidates (:303-304 sit inside
-            // `if (!candidates.empty())`): the values of the candidate-free rings before this one are still in it
-            int first = cidx;
-            while (first > 0 && sh_ncand[first - 1] == 0) --first;
-            int nrf = 0;
-            for (int r2 = first; r2 <= cidx; ++r2) nrf += sh_nrf[r2];
-            double mean_f = 0.0, std_f = 0.0;
-            if (nrf > 1) {
-                double sm = 0.0;
-                for (int r2 = first; r2 <= cidx; ++r2)
-                    for (int i = 0; i < sh_nrf[r2]; ++i) sm += sh_rf[r2][i];
-                mean_f = sm / (double)nrf;
-                for (int r2 = first; r2 <= cidx; ++r2)
-                    for (int i = 0; i < sh_nrf[r2]; ++i) std_f += (sh_rf[r2][i] - mean_f) * (sh_rf[r2][i] - mean_f);
-                std_f /= (double)(nrf - 1);
-                std_f = sqrt(std_f);
-            }
-            for (int s = 0; s < ns; ++s) {
-                PwPatchRec& r = lrec[base + s];
-                if (r.decision != 2) continue;
-                bool revert = false;
-                if (P->enable_TGR) {
-                    const double flatness = fmin(fmin((double)r.sv[0], (double)r.sv[1]), (double)r.sv[2]);
-                    const double line_variable = r.sv[1] != 0 ? (double)(r.sv[0] / r.sv[1]) : DBL_MAX;
-                    double mu = mean_f + 1.5 * std_f;
-                    double prob = 1 / (1 + exp((flatness - mu) / (mu / 10)));
-                    if (r.n_ground > 1500 && flatness < P->th_dist * P->th_dist) prob = 1.0;
-                    double prob_line = 1.0;
-                    if (line_variable > 8.0) prob_line = 0.0;
-                    revert = (prob_line * prob > 0.5) && (cidx < P->num_rings_of_interest);
-                }
-                r.decision = revert ? 1 : 0;
-            }
+    __device__ void trim(int limit) const {      // drop the oldest values beyond `limit`
+        const int exceed = *cnt - limit;
+        if (exceed > 0) {
+            *head = (*head + exceed) & (PW_STORE_CAP - 1);
+            *cnt -= exceed;
         }
     }
-    __syncthreads();
-    for (int w = lane; w < n_patches; w += blockDim.x) recs[w].decision = lrec[w].decision;
-    __syncthreads();                                        // `raw` changes hands
-    // ---- update_elevation_thr (:339-358) and update_flatness_thr (:360-376) ----
-    // Mean and standard deviation of the eight stores (<= ~1050 values each), summed SEQUENTIALLY in stored order like the
-    // reference's loops (the order is part of the parity model).  One lane per store walking its ring buffer in global memory
-    // was a chain of ~2 100 dependent-latency reads: 373 us per pass once the stores are full, two thirds of the whole ground
-    // pass.  The wave now copies the stores into LDS with coalesced loads, 512 values at a time, and the owner lanes add from
-    // there: the same additions in the same order, ~10 us.
-    double (*const sbuf)[512] = reinterpret_cast<double (*)[512]>(raw);      // [8][512]
-    __shared__ int sh_head[8], sh_cnt[8];
-    const int sid = lane < 4 ? lane : ((lane >= 8 && lane < 12) ? lane - 4 : -1);      // stores 0..3 elevation, 4..7 flatness
-    bool own = false;
-    if (sid >= 0 && sid < 4) own = sid < P->num_rings_of_interest && S->elev_cnt[sid] > 0;
-    if (sid >= 4) {
-        const int i = sid - 4;
-        own = i < P->num_rings_of_interest;
-        for (int j = 0; j <= i; ++j)
-            if (S->flat_cnt[j] <= 1) own = false;           // the reference BREAKS at the first ring with <= 1 entries
+};
+
+struct PwRingwise {                  // what the near rings' lanes hand from the first phase to the second (LDS)
+    double rf[4][64];                // per near ring: the flatness values it appends to `ringwise_flatness` (<= sectors per ring <= 64)
+    int nrf[4], ncand[4];
+};
+
+// Ground-likelihood estimation of ring cidx (:218-283), sector after sector: the decision tree and the appends to the ring's stores
+__device__ __forceinline__ void pw_ring_likelihood(const vg_ground_params& P, PwState* S, PwRing rg, int cidx, PwPatchRec* lrec,
+                                                   PwRingwise& rw) {
+    const bool is_near = cidx < P.num_rings_of_interest;
+    double* rf = rw.rf[cidx < 4 ? cidx : 0];                 // (only near rings add to it)
+    int nrf = 0, ncand = 0;
+    for (int s = 0; s < rg.sectors; ++s) {
+        PwPatchRec& r = lrec[rg.first_patch + s];
+        if (r.decision != -1) continue;                      // < num_min_pts points: all non-ground
+        const double upright = r.normal[2], elevation = r.mean[2];
+        const double flatness = pw_flatness(r);
+        double heading = 0.0;
+        for (int i = 0; i < 3; ++i) heading += (double)(r.mean[i] * r.normal[i]);
+        const bool is_upright = upright > P.uprightness_thr;
+        const bool heading_outside = heading < 0.0;
+        bool not_elevated = false, is_flat = false;
+        if (is_near) {
+            not_elevated = elevation < S->elevation_thr[cidx];
+            is_flat = flatness < S->flatness_thr[cidx];
+        }
+        if (is_upright && not_elevated && is_near) {         // :254-260
+            PwStore(S, cidx).push(elevation);
+            PwStore(S, 4 + cidx).push(flatness);
+            rf[nrf++] = flatness;
+        }
+        if (!is_upright) r.decision = 0;
+        else if (!is_near) r.decision = 1;
+        else if (!heading_outside) r.decision = 0;
+        else if (not_elevated || is_flat) r.decision = 1;
+        else { r.decision = 2; ncand++; }
     }
-    if (lane < 8) {
-        sh_head[lane] = lane < 4 ? S->elev_head[lane] : S->flat_head[lane - 4];
-        sh_cnt[lane] = lane < 4 ? S->elev_cnt[lane] : S->flat_cnt[lane - 4];
+    if (cidx < 4) { rw.nrf[cidx] = nrf; rw.ncand[cidx] = ncand; }
+}
+
+// Temporal ground revert of ring cidx's candidates (:293-305, :403-465)
+__device__ __forceinline__ void pw_ring_revert(const vg_ground_params& P, PwRing rg, int cidx, PwPatchRec* lrec, const PwRingwise& rw) {
+    if (cidx >= 4 || rw.ncand[cidx] == 0) return;
+    // `ringwise_flatness` is cleared only at the end of a ring that HAD candidates (:303-304 sit inside
+    // `if (!candidates.empty())`): the values of the candidate-free rings before this one are still in it
+    int first = cidx;
+    while (first > 0 && rw.ncand[first - 1] == 0) --first;
+    int nrf = 0;
+    for (int r2 = first; r2 <= cidx; ++r2) nrf += rw.nrf[r2];
+    double mean_f = 0.0, std_f = 0.0;
+    if (nrf > 1) {
+        double sm = 0.0;
+        for (int r2 = first; r2 <= cidx; ++r2)
+            for (int i = 0; i < rw.nrf[r2]; ++i) sm += rw.rf[r2][i];
+        mean_f = sm / (double)nrf;
+        for (int r2 = first; r2 <= cidx; ++r2)
+            for (int i = 0; i < rw.nrf[r2]; ++i) std_f += (rw.rf[r2][i] - mean_f) * (rw.rf[r2][i] - mean_f);
+        std_f = sqrt(std_f / (double)(nrf - 1));
+    }
+    for (int s = 0; s < rg.sectors; ++s) {
+        PwPatchRec& r = lrec[rg.first_patch + s];
+        if (r.decision != 2) continue;
+        bool revert = false;
+        if (P.enable_TGR) {
+            const double flatness = pw_flatness(r);
+            const double line_variable = r.sv[1] != 0 ? (double)(r.sv[0] / r.sv[1]) : DBL_MAX;
+            double mu = mean_f + 1.5 * std_f;
+            double prob = 1 / (1 + exp((flatness - mu) / (mu / 10)));
+            if (r.n_ground > 1500 && flatness < P.th_dist * P.th_dist) prob = 1.0;
+            const double prob_line = line_variable > 8.0 ? 0.0 : 1.0;
+            revert = (prob_line * prob > 0.5) && (cidx < P.num_rings_of_interest);
+        }
+        r.decision = revert ? 1 : 0;
+    }
+}
+
+// update_elevation_thr (:339-358) and update_flatness_thr (:360-376), by the whole workgroup.
+// Mean and standard deviation of the eight stores (<= ~1050 values each), summed SEQUENTIALLY in stored order like the
+// reference's loops (the order is part of the parity model).  One lane per store walking its ring buffer in global memory
+// was a chain of ~2 100 dependent-latency reads: 373 us per pass once the stores are full, two thirds of the whole ground
+// pass.  The workgroup now copies the stores into LDS with coalesced loads, 512 values at a time, and the owner lanes (lane = store
+// id; every owner's sum is its own chain) add from there: the same additions in the same order, ~10 us.
+__device__ __forceinline__ void pw_update_thresholds(const vg_ground_params& P, PwState* S, double (*sbuf)[512] /*[8]*/, int* sh_head,
+                                                     int* sh_cnt /*[8] each*/) {
+    const int lane = threadIdx.x, sid = lane < 8 ? lane : -1;
+    if (sid >= 0) {
+        const PwStore st(S, sid);
+        sh_head[sid] = *st.head;
+        sh_cnt[sid] = *st.cnt;
     }
     __syncthreads();
+    bool own = sid >= 0 && (sid & 3) < P.num_rings_of_interest;
+    if (own && sid < 4) own = sh_cnt[sid] > 0;
+    if (own && sid >= 4)
+        for (int j = 4; j <= sid; ++j)
+            if (sh_cnt[j] <= 1) own = false;                // the reference BREAKS at the first ring with <= 1 entries
     int maxcnt = 0;
     for (int t = 0; t < 8; ++t) maxcnt = max(maxcnt, sh_cnt[t]);
     const int cnt = sid >= 0 ? sh_cnt[sid] : 0;
@@ -617,7 +613,7 @@ __global__ __launch_bounds__(256) void k_pw_decide(vg_ground_params* __restrict_
         double acc = 0.0;
         for (int c0 = 0; c0 < maxcnt; c0 += 512) {
             for (int t = 0; t < 8; ++t) {
-                const double* v = t < 4 ? S->elev[t] : S->flat[t - 4];
+                const double* v = PwStore(S, t).v;
                 const int m = min(512, sh_cnt[t] - c0);
                 for (int i = lane; i < m; i += blockDim.x) sbuf[t][i] = v[(sh_head[t] + c0 + i) & (PW_STORE_CAP - 1)];
             }
@@ -639,28 +635,38 @@ __global__ __launch_bounds__(256) void k_pw_decide(vg_ground_params* __restrict_
             else { stdev = acc / (double)(cnt - 1); stdev = sqrt(stdev); }
         }
     }
-    if (own && sid < 4) {
-        const int i = sid;
-        if (i == 0) {
-            S->elevation_thr[i] = mean + 3 * stdev;
-            S->sensor_height = -mean;
-        } else
-            S->elevation_thr[i] = mean + 2 * stdev;
-        int exceed = S->elev_cnt[i] - P->max_elevation_storage;
-        if (exceed > 0) {
-            S->elev_head[i] = (S->elev_head[i] + exceed) & (PW_STORE_CAP - 1);
-            S->elev_cnt[i] -= exceed;
-        }
-    }
-    if (own && sid >= 4) {
-        const int i = sid - 4;
-        S->flatness_thr[i] = mean + stdev;
-        int exceed = S->flat_cnt[i] - P->max_flatness_storage;
-        if (exceed > 0) {
-            S->flat_head[i] = (S->flat_head[i] + exceed) & (PW_STORE_CAP - 1);
-            S->flat_cnt[i] -= exceed;
-        }
-    }
+    if (!own) return;
+    if (sid == 0) {
+        S->elevation_thr[0] = mean + 3 * stdev;
+        S->sensor_height = -mean;
+    } else if (sid < 4)
+        S->elevation_thr[sid] = mean + 2 * stdev;
+    else
+        S->flatness_thr[sid - 4] = mean + stdev;
+    PwStore(S, sid).trim(sid < 4 ? P.max_elevation_storage : P.max_flatness_storage);
+}
+
+// lane r < n_rings: sequential GLE, then TGR, for ring r.  Then the threshold update.  (256 threads: the other three waves only help
+// with the copies into LDS.)
+__global__ __launch_bounds__(256) void k_pw_decide(const vg_ground_params P, const PwGeom G, PwState* __restrict__ S,
+                                                  PwPatchRec* __restrict__ recs) {
+    const int lane = threadIdx.x;
+    __shared__ PwRingwise rw;
+    // one 48 KB buffer, two uses: the patch records while the rings are decided (each ring's lane walks its <= 54 sectors one
+    // after the other: from LDS, not through ~100 dependent reads of global memory), then the threshold stores
+    __shared__ double raw[PW_MAX_PATCHES * sizeof(PwPatchRec) / 8];
+    __shared__ int sh_head[8], sh_cnt[8];
+    PwPatchRec* const lrec = reinterpret_cast<PwPatchRec*>(raw);
+    if (lane < 4) { rw.nrf[lane] = 0; rw.ncand[lane] = 0; }
+    for (int w = lane; w < G.n_patches * (int)(sizeof(PwPatchRec) / 4); w += blockDim.x) reinterpret_cast<int*>(raw)[w] = reinterpret_cast<const int*>(recs)[w];
+    __syncthreads();
+    if (lane < G.n_rings) pw_ring_likelihood(P, S, pw_ring(P, G, lane), lane, lrec, rw);
+    __syncthreads();
+    if (lane < G.n_rings) pw_ring_revert(P, pw_ring(P, G, lane), lane, lrec, rw);
+    __syncthreads();
+    for (int w = lane; w < G.n_patches; w += blockDim.x) recs[w].decision = lrec[w].decision;
+    __syncthreads();                                        // `raw` changes hands
+    pw_update_thresholds(P, S, reinterpret_cast<double (*)[512]>(raw), sh_head, sh_cnt);
 }
 
 __global__ void k_pw_finalize(const int* __restrict__ patch_id, const unsigned char* __restrict__ inlier,
@@ -681,14 +687,16 @@ static void pw_geometry(const vg_ground_params& p, PwGeom& g) {
     g.ring_sizes[1] = (z3 - z2) / p.num_rings_each_zone[1];
     g.ring_sizes[2] = (z4 - z3) / p.num_rings_each_zone[2];
     g.ring_sizes[3] = (p.max_range - z4) / p.num_rings_each_zone[3];
-    int n = 0;
+    int n = 0, nr = 0;
     for (int k = 0; k < 4; ++k) {
         g.sector_sizes[k] = 2 * M_PI / p.num_sectors_each_zone[k];
         g.patch_base[k] = n;
+        g.ring_base[k] = nr;
         n += p.num_rings_each_zone[k] * p.num_sectors_each_zone[k];
+        nr += p.num_rings_each_zone[k];
     }
-    g.patch_base[4] = n;
-    g.n_patches = n;
+    g.patch_base[4] = g.n_patches = n;
+    g.ring_base[4] = g.n_rings = nr;
 }
 
 extern "C" {
@@ -705,21 +713,16 @@ void vg_ground_default_params(vg_ground_params* p) {   // patchworkpp.h:75-107
     p->max_flatness_storage = 1000; p->max_elevation_storage = 1000;
 }
 
-static int pw_upload(vg_ground* h) {
+static int pw_upload(vg_ground* h) {     // the geometry of h->p, and a fresh state on the device
     pw_geometry(h->p, h->g);
-    VG_CHECK(hipMemcpy(h->d_p, &h->p, sizeof(h->p), hipMemcpyHostToDevice));
-    VG_CHECK(hipMemcpy(h->d_g, &h->g, sizeof(h->g), hipMemcpyHostToDevice));
-    PwState* st = new PwState();
-    memset(st, 0, sizeof(*st));
+    std::unique_ptr<PwState> st(new PwState());      // zeroed: empty stores
     st->sensor_height = h->p.sensor_height;
     for (int i = 0; i < 4; ++i) { st->elevation_thr[i] = h->p.elevation_thr[i]; st->flatness_thr[i] = h->p.flatness_thr[i]; }
-    hipError_t e = hipMemcpy(h->d_state, st, sizeof(*st), hipMemcpyHostToDevice);
-    delete st;
-    VG_CHECK(e);
+    VG_CHECK(hipMemcpy(h->d_state, st.get(), sizeof(PwState), hipMemcpyHostToDevice));
     return VG_OK;
 }
 
-// What the kernels' fixed-size arrays can hold (sh_rf[4][64], hist[PW_MAX_PATCHES], one lane per ring, the ring buffers of PwState):
+// What the kernels' fixed-size arrays can hold (PwRingwise::rf[4][64], hist[PW_MAX_PATCHES], one lane per ring, the ring buffers of PwState):
 // every way parameters reach a handle -- vg_ground_create, vg_ground_reset -- goes through this.
 static bool pw_params_ok(const vg_ground_params* p) {
     int np = 0, nr = 0;
@@ -732,34 +735,37 @@ static bool pw_params_ok(const vg_ground_params* p) {
              p->max_elevation_storage + 64 > PW_STORE_CAP || p->max_flatness_storage + 64 > PW_STORE_CAP);
 }
 
+static int pw_alloc(vg_ground* h) {      // every device buffer of a handle; what a failure leaves behind, vg_ground_destroy frees
+    const size_t n = (size_t)h->max_points;
+    VG_CHECK(hipMalloc(&h->d_state, sizeof(PwState)));
+    VG_CHECK(hipMalloc(&h->d_patch_id, sizeof(int) * n));
+    VG_CHECK(hipMalloc(&h->d_count, sizeof(int) * PW_MAX_PATCHES));
+    VG_CHECK(hipMemset(h->d_count, 0, sizeof(int) * PW_MAX_PATCHES));
+    VG_CHECK(hipMalloc(&h->d_offset, sizeof(int) * (PW_MAX_PATCHES + 1)));
+    VG_CHECK(hipMalloc(&h->d_cursor, sizeof(int) * PW_MAX_PATCHES));
+    VG_CHECK(hipMalloc(&h->d_keys, sizeof(unsigned long long) * n));
+    VG_CHECK(hipMalloc(&h->d_inlier, n));
+    VG_CHECK(hipMalloc(&h->d_rec, sizeof(PwPatchRec) * PW_MAX_PATCHES));
+    return VG_OK;
+}
+
 int vg_ground_create(vg_ground** out, const vg_ground_params* p, int max_points) {
     if (!out || !p || max_points <= 0 || !pw_params_ok(p)) return VG_ERR_ARG;
     vg_ground* h = new vg_ground();
     memset(h, 0, sizeof(*h));
     h->p = *p;
     h->max_points = max_points;
-    VG_CHECK(hipMalloc(&h->d_p, sizeof(vg_ground_params)));
-    VG_CHECK(hipMalloc(&h->d_g, sizeof(PwGeom)));
-    VG_CHECK(hipMalloc(&h->d_state, sizeof(PwState)));
-    VG_CHECK(hipMalloc(&h->d_patch_id, sizeof(int) * (size_t)max_points));
-    VG_CHECK(hipMalloc(&h->d_count, sizeof(int) * PW_MAX_PATCHES));
-    VG_CHECK(hipMemset(h->d_count, 0, sizeof(int) * PW_MAX_PATCHES));
-    VG_CHECK(hipMalloc(&h->d_offset, sizeof(int) * (PW_MAX_PATCHES + 1)));
-    VG_CHECK(hipMalloc(&h->d_cursor, sizeof(int) * PW_MAX_PATCHES));
-    VG_CHECK(hipMalloc(&h->d_keys, sizeof(unsigned long long) * (size_t)max_points));
-    VG_CHECK(hipMalloc(&h->d_inlier, (size_t)max_points));
-    VG_CHECK(hipMalloc(&h->d_rec, sizeof(PwPatchRec) * PW_MAX_PATCHES));
-    int rc = pw_upload(h);
-    if (rc) return rc;
-    *out = h;
-    return VG_OK;
+    int rc = pw_alloc(h);
+    if (rc == VG_OK) rc = pw_upload(h);
+    if (rc == VG_OK) *out = h;
+    else vg_ground_destroy(h);           // (hipFree of a pointer still null is harmless)
+    return rc;
 }
 
 void vg_ground_destroy(vg_ground* h) {
     if (!h) return;
-    (void)hipFree(h->d_p); (void)hipFree(h->d_g); (void)hipFree(h->d_state); (void)hipFree(h->d_patch_id);
-    (void)hipFree(h->d_count); (void)hipFree(h->d_offset); (void)hipFree(h->d_cursor); (void)hipFree(h->d_keys);
-    (void)hipFree(h->d_inlier); (void)hipFree(h->d_rec);
+    (void)hipFree(h->d_state); (void)hipFree(h->d_patch_id); (void)hipFree(h->d_count); (void)hipFree(h->d_offset);
+    (void)hipFree(h->d_cursor); (void)hipFree(h->d_keys); (void)hipFree(h->d_inlier); (void)hipFree(h->d_rec);
     delete h;
 }
 
@@ -779,19 +785,20 @@ int vg_ground_estimate(vg_ground* h, const float* d_points, int n, int stride, d
     hipStream_t st = (hipStream_t)stream;
     if (n == 0) return VG_OK;
     const int nb = vg_div_up(n, 256);
-    hipLaunchKernelGGL(k_pw_classify, dim3(nb), dim3(256), 0, st, d_points, n, stride, z_offset, h->d_p, h->d_g,
+    hipLaunchKernelGGL(k_pw_classify, dim3(nb), dim3(256), 0, st, d_points, n, stride, z_offset, h->p, h->g,
                        h->d_state, h->d_patch_id, h->d_count, h->d_inlier);
     hipLaunchKernelGGL(k_pw_offsets, dim3(1), dim3(64), 0, st, h->d_count, h->d_offset, h->d_cursor, h->g.n_patches);
     hipLaunchKernelGGL(k_pw_scatter, dim3(nb), dim3(256), 0, st, d_points, n, stride, z_offset, h->d_patch_id,
                        h->d_offset, h->d_cursor, h->d_keys);
     {
         VG_MAX_DYNAMIC_LDS(k_pw_sort_big, PW_BIG_LDS_POINTS * 8);
-        hipLaunchKernelGGL(k_pw_sort_big, dim3(h->g.n_patches), dim3(1024), PW_BIG_LDS_POINTS * 8, st, h->d_p, h->d_offset, h->d_keys);
+        hipLaunchKernelGGL(k_pw_sort_big, dim3(h->g.n_patches), dim3(1024), PW_BIG_LDS_POINTS * 8, st, h->p.num_min_pts, h->d_offset,
+                           h->d_keys);
     }
     // k_pw_patch reads x, y straight from d_points and z from the key (already offset)
-    hipLaunchKernelGGL(k_pw_patch, dim3(h->g.n_patches), dim3(PW_T), 0, st, d_points, stride, h->d_p, h->d_g, h->d_state,
+    hipLaunchKernelGGL(k_pw_patch, dim3(h->g.n_patches), dim3(PW_T), 0, st, d_points, stride, h->p, h->g, h->d_state,
                        h->d_offset, h->d_keys, h->d_inlier, h->d_rec);
-    hipLaunchKernelGGL(k_pw_decide, dim3(1), dim3(256), 0, st, h->d_p, h->d_g, h->d_state, h->d_rec);
+    hipLaunchKernelGGL(k_pw_decide, dim3(1), dim3(256), 0, st, h->p, h->g, h->d_state, h->d_rec);
     hipLaunchKernelGGL(k_pw_finalize, dim3(nb), dim3(256), 0, st, h->d_patch_id, h->d_inlier, h->d_rec, n, d_ground_mask);
     VG_LAUNCH_CHECK();
     return VG_OK;
@@ -801,19 +808,15 @@ int vg_ground_estimate(vg_ground* h, const float* d_points, int n, int stride, d
 int vg_ground_get_state(vg_ground* h, double* h_out17, void* stream) {
     if (!h || !h_out17) return VG_ERR_ARG;
     VG_CHECK(hipStreamSynchronize((hipStream_t)stream));
-    PwState* st = new PwState();
-    hipError_t e = hipMemcpy(st, h->d_state, sizeof(PwState), hipMemcpyDeviceToHost);
-    if (e == hipSuccess) {
-        h_out17[0] = st->sensor_height;
-        for (int i = 0; i < 4; ++i) {
-            h_out17[1 + i] = st->elevation_thr[i];
-            h_out17[5 + i] = st->flatness_thr[i];
-            h_out17[9 + i] = st->elev_cnt[i];
-            h_out17[13 + i] = st->flat_cnt[i];
-        }
+    PwStateHead st;                      // what stands in front of the stores
+    VG_CHECK(hipMemcpy(&st, h->d_state, sizeof(st), hipMemcpyDeviceToHost));
+    h_out17[0] = st.sensor_height;
+    for (int i = 0; i < 4; ++i) {
+        h_out17[1 + i] = st.elevation_thr[i];
+        h_out17[5 + i] = st.flatness_thr[i];
+        h_out17[9 + i] = st.elev_cnt[i];
+        h_out17[13 + i] = st.flat_cnt[i];
     }
-    delete st;
-    VG_CHECK(e);
     return VG_OK;
 }
 
@@ -847,19 +850,15 @@ int vg_ground_num_patches(const vg_ground* h) { return h ? h->g.n_patches : 0; }
 int vg_ground_get_patch_info(vg_ground* h, float* h_out, void* stream) {
     if (!h || !h_out) return VG_ERR_ARG;
     VG_CHECK(hipStreamSynchronize((hipStream_t)stream));
-    PwPatchRec* r = new PwPatchRec[PW_MAX_PATCHES];
-    hipError_t e = hipMemcpy(r, h->d_rec, sizeof(PwPatchRec) * h->g.n_patches, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) {
-        for (int i = 0; i < h->g.n_patches; ++i) {
-            float* o = h_out + (size_t)i * 12;
-            o[0] = (float)r[i].n;
-            o[1] = (float)r[i].n_ground;
-            for (int k = 0; k < 3; ++k) { o[2 + k] = r[i].normal[k]; o[5 + k] = r[i].mean[k]; o[8 + k] = r[i].sv[k]; }
-            o[11] = (float)r[i].decision;
-        }
+    std::vector<PwPatchRec> r(h->g.n_patches);
+    VG_CHECK(hipMemcpy(r.data(), h->d_rec, sizeof(PwPatchRec) * r.size(), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < r.size(); ++i) {
+        float* o = h_out + i * 12;
+        o[0] = (float)r[i].n;
+        o[1] = (float)r[i].n_ground;
+        for (int k = 0; k < 3; ++k) { o[2 + k] = r[i].normal[k]; o[5 + k] = r[i].mean[k]; o[8 + k] = r[i].sv[k]; }
+        o[11] = (float)r[i].decision;
     }
-    delete[] r;
-    VG_CHECK(e);
     return VG_OK;
 }
 
