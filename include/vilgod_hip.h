@@ -485,6 +485,38 @@ int vg_knn_host(const float* h_query, int nq, int qstride, const float* h_target
  * only when this value is strictly greater. */
 double vg_knn_prune_bound_host(double box_d2);
 
+/* DBSCAN: sklearn.cluster.DBSCAN, the second clustering model the reference's cluster_utils.py imports (src/utils/cluster_utils.py:4-5),
+ * on the handle's 0.4 m grid (csrc/cluster_dbscan.inc).  The definition -- what sklearn's dbscan_inner computes, stated without its
+ * traversal (it grows clusters to completion one seed at a time in row order; a border row is claimed by the first cluster that
+ * reaches it):
+ *   input     d_points [n, stride] float32; the first dim = 3, 4 or 5 columns are the clustering space, x, y, z first (5 = the
+ *             two-frame points_seq).  Finite by contract, as for vg_cluster_grid: nothing is read back to check it.
+ *   pair      both rows widened exactly to double; d2 = ((dx*dx + dy*dy) + dz*dz [+ d4*d4 [+ d5*d5]]), left to right, no fused
+ *             multiply-add (csrc/dbscan_pair.inc, one __host__ __device__ text for the kernels and the host twin); neighbours iff
+ *             d2 <= eps2, INCLUSIVE, eps2 = eps * eps formed in double.  A row is its own neighbour.
+ *   core      row i is a core sample iff it has at least min_samples neighbours, itself and duplicates counted
+ *   clusters  the connected components of the graph on the core rows whose edges are neighbour pairs; labels 0, 1, ... in ascending
+ *             order of each component's LOWEST CORE ROW (index in the caller's array)
+ *   border    a non-core row with at least one core neighbour takes the smallest label among its core neighbours; every other
+ *             non-core row gets -1
+ *   outputs   on the device, in the caller's row order: d_labels int32 [n]; d_core uint8 [n] (1 = core sample); d_n_clusters int32 [1];
+ *             d_probs float64 [n] or NULL: 1.0 for a labelled row, 0.0 for noise.  sklearn's DBSCAN has no probabilities_; the
+ *             reference reads cluster_info.probabilities_ after fit, so this is this project's own convention.
+ * vg_cluster_dbscan builds the grid over d_points itself (the handle's grid is replaced, as by vg_cluster_mst_nd, and afterwards
+ * serves vg_cluster_ball_count / _nearest / _knn over these points) and queues the rest on `stream`: no read-back, no synchronisation,
+ * no allocation (the working arrays are the handle's), every launch sized from n -- the call can be captured into a graph -- and only
+ * integer atomics whose result is a set property or a minimum: the same bits on every run.  Every pointer walk of the union-find is
+ * bounded by n; should one overrun (it cannot: parent[p] <= p throughout), d_n_clusters holds -1 and the labels are undefined.
+ * One call at a time per handle.
+ * vg_dbscan_host: HOST ONLY, no GPU: all pairs, no grid, a sequential union-find, the same pair function.  The two agree exactly.
+ * VG_ERR_ARG (nothing launched): eps NaN, <= 0 or with ceil(eps / 0.4) > 8 (the grid's reach limit, 3.2 m, as
+ * vg_cluster_ball_count); min_samples < 1; dim outside 3..5; stride < dim; n < 0; n > the handle's max_points; null pointers (d_probs /
+ * h_probs may be NULL).  n == 0: VG_OK, n_clusters 0. */
+int vg_cluster_dbscan(vg_cluster* h, const float* d_points, int n, int stride, int dim, double eps, int min_samples, int32_t* d_labels,
+                      uint8_t* d_core, double* d_probs, int32_t* d_n_clusters, void* stream);
+int vg_dbscan_host(const float* h_points, int n, int stride, int dim, double eps, int min_samples, int32_t* h_labels, uint8_t* h_core,
+                   double* h_probs, int32_t* h_n_clusters);
+
 /* HOST ONLY, no GPU (like vg_hdbscan_tree_host): the geometry vg_cluster_mst[_nd] prunes with, evaluated on the CPU by the very
  * functions its kernels call, so that the bounds can be checked without a device.  Pair i = (point i, query i), finite float32.
  *   h_origin_in [3] f64 or NULL: the grid's origin; NULL: the origin the kernels derive from the float32 extremes h_bbox_lo/hi [3]

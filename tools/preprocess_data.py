@@ -96,6 +96,7 @@ def main(argv=None):
                                    cu_reserve=int(dev.get('cu_reserve', 0)), cu_tower=dev.get('cu_tower', 'complement'),
                                    pack=dev.get('pack', 'host'), text=dev.get('text', 'host'),
                                    text_dtype=dev.get('text_dtype', 'f32'))
+    logger.info(f"Clustering model: {type(pipeline.cluster_model).__name__}({', '.join(f'{k}={v!r}' for k, v in pipeline._mcfg.items())})")
     logger.info(f'CLIP weights: {pipeline.clip.weights_source}')
     from vilgod_amd import clip_weights
     tc = pipeline.clip.encoder.cfg

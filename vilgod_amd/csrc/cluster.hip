@@ -20,7 +20,8 @@
 //                         (w2, pair d2, min id, max id) so the tree is unique and equals the oracle's
 //        radix sort of the n - 1 edges by weight
 // Beside the clustering, on the same grid and tree over a TARGET set (vg_cluster_grid): the fixed-radius queries k_cl_ball_count /
-// k_cl_nearest, and the K nearest targets without a radius, k_cl_knn (cluster_knn.inc).
+// k_cl_nearest, and the K nearest targets without a radius, k_cl_knn (cluster_knn.inc).  DBSCAN, the reference's other clustering
+// model, on the same grid: k_db_* (cluster_dbscan.inc).
 // The hierarchy stage (K2d) takes the sorted edges from here: csrc/hdbscan_device.hip on the device, csrc/hdbscan_tree.cpp on the host.
 // The development build adds dev/cluster_dev.inc: the per-point k-NN walk the cooperative phases replaced, and the A/B switches.
 //
@@ -204,6 +205,15 @@ __global__ void k_cl_bbox(const float* __restrict__ pts, int n, int stride, ClGr
         atomicMin(&g->kmin[a], vg_fkey(lo));
         atomicMax(&g->kmax[a], vg_fkey(hi));
     }
+}
+
+// the ClGrid a build starts from, written on the device: what cl_build_grid otherwise copies from the host, for calls that are captured
+// into a graph (a copy node would read the host bytes again at every replay)
+__global__ void k_cl_grid_reset(ClGrid* g) {
+    if (threadIdx.x != 0) return;
+    g->ox = 0.0; g->oy = 0.0; g->oz = 0.0;
+    for (int a = 0; a < 3; ++a) { g->kmin[a] = 0xFFFFFFFFu; g->kmax[a] = 0u; }
+    g->inf = __hiloint2double(0x7FF00000, 0);
 }
 
 __global__ void k_cl_grid(ClGrid* g) {
@@ -1385,11 +1395,12 @@ static int cl_alloc(vg_cluster* h) {
     VG_CHECK(hipMalloc(&h->d_mst_idx_s, 4 * n));
     VG_CHECK(hipHostMalloc((void**)&h->h_counter, 64));
     if (getenv("VG_CLUSTER_DEBUG")) VG_CHECK(hipMalloc(&h->d_dbg, 4 * n));
-    size_t t1 = 0, t2 = 0, t3 = 0;
+    size_t t1 = 0, t2 = 0, t3 = 0, t4 = 0;
     VG_CHECK(rocprim::radix_sort_pairs(nullptr, t1, h->d_code, h->d_code_s, h->d_perm_in, h->d_perm, n, 0, 24));
     VG_CHECK(rocprim::radix_sort_pairs(nullptr, t2, h->d_mst_w, h->d_mst_w_s, h->d_mst_idx, h->d_mst_idx_s, n, 0, 64));
     VG_CHECK(rocprim::inclusive_scan(nullptr, t3, h->d_cell_start, h->d_cell_start, (size_t)(CL_NCODES + 1), MinOp()));
-    h->temp_bytes = std::max(t1, std::max(t2, t3)) + 256;
+    VG_CHECK(rocprim::exclusive_scan(nullptr, t4, h->d_sel_a, h->d_sel_b, 0, n, rocprim::plus<int>()));      // cluster_dbscan.inc
+    h->temp_bytes = std::max(std::max(t1, t4), std::max(t2, t3)) + 256;
     VG_CHECK(hipMalloc(&h->d_temp, h->temp_bytes));
     return VG_OK;
 }
@@ -1424,13 +1435,18 @@ void vg_cluster_destroy(vg_cluster* h) {
 }  // extern "C"
 
 // bbox -> grid origin -> Morton codes -> radix sort -> sorted points + dense cell-start table
-static int cl_build_grid(vg_cluster* h, const float* d_points, int n, int stride, int dim, hipStream_t st) {
+// (device_reset: the starting ClGrid is written by a kernel instead of copied from the host -- vg_cluster_dbscan, which can be captured)
+static int cl_build_grid(vg_cluster* h, const float* d_points, int n, int stride, int dim, hipStream_t st, bool device_reset = false) {
     const int nb = vg_div_up(n, 256);
-    ClGrid g0;
-    memset(&g0, 0, sizeof(g0));
-    for (int a = 0; a < 3; ++a) { g0.kmin[a] = 0xFFFFFFFFu; g0.kmax[a] = 0u; }
-    g0.inf = INFINITY;
-    VG_CHECK(hipMemcpyAsync(h->d_grid, &g0, sizeof(g0), hipMemcpyHostToDevice, st));
+    if (device_reset) {
+        hipLaunchKernelGGL(k_cl_grid_reset, dim3(1), dim3(64), 0, st, h->d_grid);
+    } else {
+        ClGrid g0;
+        memset(&g0, 0, sizeof(g0));
+        for (int a = 0; a < 3; ++a) { g0.kmin[a] = 0xFFFFFFFFu; g0.kmax[a] = 0u; }
+        g0.inf = INFINITY;
+        VG_CHECK(hipMemcpyAsync(h->d_grid, &g0, sizeof(g0), hipMemcpyHostToDevice, st));
+    }
     hipLaunchKernelGGL(k_cl_bbox, dim3(std::min(nb, 64)), dim3(256), 0, st, d_points, n, stride, h->d_grid);
     hipLaunchKernelGGL(k_cl_grid, dim3(1), dim3(64), 0, st, h->d_grid);
     hipLaunchKernelGGL(k_cl_codes, dim3(nb), dim3(256), 0, st, d_points, n, stride, h->d_grid, h->d_code, h->d_perm_in);
@@ -1750,3 +1766,6 @@ int vg_cluster_mst(vg_cluster* h, const float* d_points, int n, int stride, int 
 }
 
 }  // extern "C"
+
+#include "dbscan_pair.inc"         // the DBSCAN pair test, __host__ __device__
+#include "cluster_dbscan.inc"      // DBSCAN on the grid: k_db_*, vg_cluster_dbscan, vg_dbscan_host

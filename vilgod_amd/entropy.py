@@ -209,14 +209,19 @@ class TwoFrameClusterer:
         seq = self.cluster_input(fnr, X_list, ent_list)
         n = X_list[fnr].shape[0]
         m = seq.shape[0]
-        if m < 2:
+        dbscan = hasattr(self.model, 'labels_device')
+        if m < (1 if dbscan else 2):                  # (one row can be a DBSCAN cluster: min_samples 1)
             return np.full(n, -1, np.int64), np.zeros(n)
-        lo, hi, w2 = self.model.mst(seq, dim=5)
-        on_device = getattr(self.model, 'hierarchy', 'host') == 'device'
-        if on_device:        # the hierarchy stage as kernels: the tree stays on the GPU, the label transfer below is a device gather
-            d_lab, d_prob, _ = self.model.tree_device(lo, hi, w2, m)
+        if dbscan:           # a DBSCAN model: one queued call on the 5-D rows, the transfer below is a device gather
+            on_device = True
+            d_lab, d_prob, _, _ = self.model.labels_device(seq, dim=5)
         else:
-            lab_seq, prob_seq, _ = self.model.tree(lo.cpu().numpy(), hi.cpu().numpy(), w2.cpu().numpy(), m)
+            lo, hi, w2 = self.model.mst(seq, dim=5)
+            on_device = getattr(self.model, 'hierarchy', 'host') == 'device'
+            if on_device:    # the hierarchy stage as kernels: the tree stays on the GPU, the label transfer below is a device gather
+                d_lab, d_prob, _ = self.model.tree_device(lo, hi, w2, m)
+            else:
+                lab_seq, prob_seq, _ = self.model.tree(lo.cpu().numpy(), hi.cpu().numpy(), w2.cpu().numpy(), m)
         self.model.grid(seq)
         Xf = X_list[fnr]
         o = spatial_order(Xf)

@@ -31,43 +31,16 @@ def selection_options(cluster_selection_method='eom', allow_single_cluster=False
     return (1 if cluster_selection_method == 'leaf' else 0, int(bool(allow_single_cluster)), int(max_cluster_size) if max_cluster_size else 0)
 
 
-class HDBSCAN:
-    def __init__(self, min_cluster_size=5, min_samples=None, cluster_selection_epsilon=0.0, metric='euclidean',
-                 core_dist_n_jobs=None, max_points=400_000, device='cuda', hierarchy='host', cluster_selection_method='eom',
-                 allow_single_cluster=False, max_cluster_size=None, **unused):
-        if metric != 'euclidean':
-            raise NotImplementedError('only the euclidean metric of the reference configuration is implemented')
-        for k in unused:
-            if k not in ('alpha', 'algorithm', 'leaf_size', 'approx_min_span_tree', 'gen_min_span_tree', 'prediction_data', 'memory'):
-                raise TypeError(f'unexpected keyword {k}')
-        # (selection, allow_single_cluster, max_cluster_size) as vg_hdbscan_tree_host_ex / _device_ex take them
-        self.selection_args = selection_options(cluster_selection_method, allow_single_cluster, max_cluster_size)
-        self.cluster_selection_method = cluster_selection_method
-        self.allow_single_cluster = bool(allow_single_cluster)
-        self.max_cluster_size = self.selection_args[2] or None
-        self.min_cluster_size = int(min_cluster_size)
-        self.min_samples = int(min_samples) if min_samples is not None else self.min_cluster_size
-        if not 1 <= self.min_samples <= CLUSTER_MAX_K:
-            raise NotImplementedError(f'min_samples must be in [1, {CLUSTER_MAX_K}] (the neighbour list of an isolated query is one '
-                                      'entry per lane of a wave)')
-        self.cluster_selection_epsilon = float(cluster_selection_epsilon)
-        self.device = torch.device(device)
-        self.max_points = int(max_points)
-        # `fit`'s hierarchy stage: 'host' (csrc/hdbscan_tree.cpp) or 'device' (csrc/hdbscan_device.hip: the tree stays on the GPU);
-        # identical results.  (The fused pipeline chooses for itself: PseudoLabelPipeline(hierarchy=...).)
-        if hierarchy not in ('host', 'device'):
-            raise ValueError("hierarchy: 'host' or 'device'")
-        if self.min_cluster_size > 32 or self.max_points > (1 << 20):       # what the device stage holds (include/vilgod_hip.h)
-            hierarchy = 'host'
-        self.hierarchy = hierarchy
-        self._hier = None
+class GridQueries:
+    """What every clustering model of this package owns and offers besides its clustering: a `vg_cluster` handle (`self._h`, for up to
+    `self.max_points` points on `self.device`) and the queries on its cell grid that `EntropyScorer`, `TwoFrameClusterer` and
+    `vilgod_amd.knn` call on the pipeline's model."""
+
+    def _create_handle(self):
         h = ctypes.c_void_p()
         with torch.cuda.device(self.device):
             check(lib.vg_cluster_create(ctypes.byref(h), self.max_points), 'vg_cluster_create')
         self._h = h
-        self.labels_ = None
-        self.probabilities_ = None
-        self.n_rounds_ = 0
 
     def __del__(self):
         h = getattr(self, '_h', None)
@@ -119,6 +92,42 @@ class HDBSCAN:
         check(lib.vg_cluster_knn(self._h, ptr(Q), nq, Q.stride(0) if nq else 3, K, float(np.float32(max_d2)), ptr(idx), ptr(d2),
                                  stream_ptr(stream)), 'vg_cluster_knn')
         return idx, d2
+
+
+class HDBSCAN(GridQueries):
+    def __init__(self, min_cluster_size=5, min_samples=None, cluster_selection_epsilon=0.0, metric='euclidean',
+                 core_dist_n_jobs=None, max_points=400_000, device='cuda', hierarchy='host', cluster_selection_method='eom',
+                 allow_single_cluster=False, max_cluster_size=None, **unused):
+        if metric != 'euclidean':
+            raise NotImplementedError('only the euclidean metric of the reference configuration is implemented')
+        for k in unused:
+            if k not in ('alpha', 'algorithm', 'leaf_size', 'approx_min_span_tree', 'gen_min_span_tree', 'prediction_data', 'memory'):
+                raise TypeError(f'unexpected keyword {k}')
+        # (selection, allow_single_cluster, max_cluster_size) as vg_hdbscan_tree_host_ex / _device_ex take them
+        self.selection_args = selection_options(cluster_selection_method, allow_single_cluster, max_cluster_size)
+        self.cluster_selection_method = cluster_selection_method
+        self.allow_single_cluster = bool(allow_single_cluster)
+        self.max_cluster_size = self.selection_args[2] or None
+        self.min_cluster_size = int(min_cluster_size)
+        self.min_samples = int(min_samples) if min_samples is not None else self.min_cluster_size
+        if not 1 <= self.min_samples <= CLUSTER_MAX_K:
+            raise NotImplementedError(f'min_samples must be in [1, {CLUSTER_MAX_K}] (the neighbour list of an isolated query is one '
+                                      'entry per lane of a wave)')
+        self.cluster_selection_epsilon = float(cluster_selection_epsilon)
+        self.device = torch.device(device)
+        self.max_points = int(max_points)
+        # `fit`'s hierarchy stage: 'host' (csrc/hdbscan_tree.cpp) or 'device' (csrc/hdbscan_device.hip: the tree stays on the GPU);
+        # identical results.  (The fused pipeline chooses for itself: PseudoLabelPipeline(hierarchy=...).)
+        if hierarchy not in ('host', 'device'):
+            raise ValueError("hierarchy: 'host' or 'device'")
+        if self.min_cluster_size > 32 or self.max_points > (1 << 20):       # what the device stage holds (include/vilgod_hip.h)
+            hierarchy = 'host'
+        self.hierarchy = hierarchy
+        self._hier = None
+        self._create_handle()
+        self.labels_ = None
+        self.probabilities_ = None
+        self.n_rounds_ = 0
 
     # ---- GPU stage ---------------------------------------------------------------------------------
     def mst(self, X, want_core=False, stream=None, dim=3):

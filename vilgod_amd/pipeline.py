@@ -30,6 +30,7 @@ from .frame_state import (FrameState, pack_clusters, vote, static_from_entropy, 
                           sublist_offsets, PACK_MAX_LABEL_BOUND)
 from . import patchworkpp as gpw
 from .hdbscan import HDBSCAN
+from .dbscan import DBSCAN, is_dbscan_target
 from .projection import RealisticProjection, VIEWS_4, VIEWS_6, check_image_size
 from .clip_wrapper import ClipWrapper
 
@@ -101,7 +102,31 @@ def _get(cfg, key, default=None):
     return getattr(cfg, key, default) if hasattr(cfg, key) else default
 
 
+def cluster_model_spec(model_cfg, hierarchy=None):
+    """`clustering.model` of a preprocessor config -> (class, keyword arguments) of the clustering model, the way the reference's
+    `hydra.utils.instantiate` reads it: a `_target_` whose last component is `DBSCAN` (`sklearn.cluster.DBSCAN`,
+    `vilgod_amd.dbscan.DBSCAN`) names `vilgod_amd.dbscan.DBSCAN`, built from the remaining keys; anything else, an absent key included,
+    is `vilgod_amd.hdbscan.HDBSCAN` with its hierarchy stage ('device' unless VILGOD_HIERARCHY or `hierarchy` says 'host').  DBSCAN has
+    no hierarchy stage: `hierarchy` is ignored for it."""
+    mcfg = dict(model_cfg)
+    target = mcfg.pop('_target_', None)
+    if is_dbscan_target(target):
+        return DBSCAN, mcfg
+    # hierarchy stage: 'device' (csrc/hdbscan_device.hip: the tree never leaves the GPU; default) or 'host' (csrc/hdbscan_tree.cpp in
+    # the frame's thread) -- the same labels and probabilities bit for bit (tests/test_hierarchy.py); the device stage takes 0.9 ms of
+    # a 150k-point frame's latency instead of 2.2 and costs the stream of frames nothing (LAB_NOTES.md section 0).  The device stage
+    # holds min_cluster_size <= 32 and <= 2^20 points; beyond that the host stage runs (HDBSCAN decides).
+    hierarchy = str(os.environ.get('VILGOD_HIERARCHY', 'device') if hierarchy is None else hierarchy)
+    if hierarchy not in ('host', 'device'):
+        raise ValueError("hierarchy: 'host' or 'device'")
+    mcfg['hierarchy'] = hierarchy
+    return HDBSCAN, mcfg
+
+
 class PseudoLabelPipeline:
+    """`clustering.model._target_` chooses the clustering model (`cluster_model_spec`): HDBSCAN, or DBSCAN for a target named so.  With
+    a DBSCAN model `self.hierarchy` is None, and `hierarchy=` and VILGOD_HIERARCHY are ignored: there is no hierarchy stage."""
+
     def __init__(self, preprocessor_cfg=None, device='cuda:0', vit_dtype='f16', n_views=4, max_points=300_000,
                  clip_model_path='../models/clip/', min_range=1.5, z_offset=1.723, plane_seed=666, clip=None,
                  box_mode='reference', box_workers=4, vit_graph=False, angle_mode='reference', cu_reserve=None, cu_tower=None,
@@ -117,18 +142,9 @@ class PseudoLabelPipeline:
         self._pw_params = params
         self.ground_model = gpw.patchworkpp(params, max_points=self.max_points, device=self.device)
         ccfg = _get(cfg, 'clustering')
-        mcfg = dict(_get(ccfg, 'model'))
-        mcfg.pop('_target_', None)
-        # hierarchy stage: 'device' (csrc/hdbscan_device.hip: the tree never leaves the GPU; default) or 'host' (csrc/hdbscan_tree.cpp in
-        # the frame's thread) -- the same labels and probabilities bit for bit (tests/test_hierarchy.py); the device stage takes 0.9 ms of
-        # a 150k-point frame's latency instead of 2.2 and costs the stream of frames nothing (LAB_NOTES.md section 0).  The device stage
-        # holds min_cluster_size <= 32 and <= 2^20 points; beyond that the host stage runs (HDBSCAN decides).
-        hierarchy = str(os.environ.get('VILGOD_HIERARCHY', 'device') if hierarchy is None else hierarchy)
-        if hierarchy not in ('host', 'device'):
-            raise ValueError("hierarchy: 'host' or 'device'")
-        mcfg['hierarchy'] = hierarchy
-        self.cluster_model = HDBSCAN(max_points=self.max_points, device=self.device, **mcfg)
-        self.hierarchy = self.cluster_model.hierarchy
+        self._model_cls, mcfg = cluster_model_spec(_get(ccfg, 'model'), hierarchy)
+        self.cluster_model = self._model_cls(max_points=self.max_points, device=self.device, **mcfg)
+        self.hierarchy = self.cluster_model.hierarchy      # 'host' / 'device'; None: a DBSCAN model
         self.prob_threshold = float(_get(ccfg, 'propability_threshold', 0.3))
         # cluster packing (labels -> ids / packed index lists / offsets) and the valid clusters' sub-lists: 'host' (the labels come down,
         # csrc/hdbscan_tree.cpp vg_pack_clusters_host groups them, the lists go up again; default) or 'device' (csrc/pack.hip: labels
@@ -200,7 +216,7 @@ class PseudoLabelPipeline:
         ViT workspace + weights, RANSAC scratch): handles are not thread-safe, like the reference objects."""
         import copy
         w = copy.copy(self)
-        w.cluster_model = HDBSCAN(max_points=self.max_points, device=self.device, **self._mcfg)
+        w.cluster_model = self._model_cls(max_points=self.max_points, device=self.device, **self._mcfg)
         w.projection = RealisticProjection(_get(self.cfg, 'lidar_image_projection'), device=self.device,
                                            views=VIEWS_4 if self._n_views == 4 else VIEWS_6, angle_mode=self.angle_mode)
         w.clip = self.clip.view()                # shared read-only weights, own workspace
@@ -501,6 +517,14 @@ class PseudoLabelPipeline:
         """d_X: [M,>=3] CUDA float32 (points_ref_wo_ground).  -> labels, probs: host arrays, or -- pack='device' with the device
         hierarchy -- the CUDA tensors the hierarchy stage wrote, handed on as they are (`label` packs them where they lie)."""
         n = d_X.shape[0]
+        if isinstance(self.cluster_model, DBSCAN):       # one queued call; pack='device' takes the tensors where they lie
+            d_labels, d_probs, _, _ = self.cluster_model.labels_device(d_X)
+            self._mark('dbscan_kernels')
+            if self.pack == 'device':
+                return d_labels, d_probs
+            labels, probs = d_labels.cpu().numpy(), d_probs.cpu().numpy()
+            self._mark('labels_d2h')
+            return labels, probs
         if n < 2:
             return np.full(n, -1, np.int64), np.zeros(n)
         lo, hi, w2 = self.cluster_model.mst(d_X)
@@ -932,7 +956,9 @@ class PseudoLabelPipeline:
             # for every selection option: excess of mass (with or without max_cluster_size) and 'leaf' both select clusters none of
             # which contains another, each of >= min_cluster_size points; allow_single_cluster adds only the root ALONE (label 0,
             # also on a frame of fewer than min_cluster_size points: the + 1)
-            bound = n // max(self.cluster_model.min_cluster_size, 1) + 1
+            # (a DBSCAN cluster needs only one core row: its model says n + 1)
+            model_bound = getattr(self.cluster_model, 'label_bound', None)
+            bound = model_bound(n) if model_bound is not None else n // max(self.cluster_model.min_cluster_size, 1) + 1
             if label_bound is not None:
                 bound = int(label_bound)
                 if bound > PACK_MAX_LABEL_BOUND:
