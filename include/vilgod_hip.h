@@ -273,6 +273,21 @@ int vg_clip_scores(const float* d_feat, int n, int dim, const float* d_text, int
  * vg_vit_classify_graph uses vg_clip_scores up to 64 classes and this entry point above. */
 int vg_clip_scores_wide(const float* d_feat, int n, int dim, const float* d_text, int n_classes, float* d_probs,
                         int32_t* d_top1, float* d_top1_score, void* stream);
+/* The top_k classes of every crop (clip_utils.py:49-61: np.argpartition(img_score, -top_k)[-top_k:] ordered by np.argsort(-scores)),
+ * selected on the device from the table either kernel above wrote.  d_probs [n, n_classes]; row i of d_idx / d_score [n, top_k]
+ * holds the top_k classes of crop i under the strict total order (probability descending, class index ascending), entry 0 the best,
+ * d_score each class's own float32 bits from the table.  A NaN probability orders behind every number (NaNs among themselves by
+ * index) and is written as it stands; -0.0 and +0.0 are equal, the index decides.  Column 0 therefore equals d_top1 / d_top1_score
+ * of vg_clip_scores[_wide] bit for bit, and a row whose top_k + 1 largest probabilities are distinct equals the reference's.
+ * vg_clip_topk: device pointers, ONE launch on `stream` (csrc/clip_topk.hip: one wave per crop, top_k shuffle rounds), its grid sized
+ * from n alone: no atomics, no read-back, no allocation, no scratch -- the same bits on every run, and it can be captured.
+ * vg_clip_topk_host: the same arguments over host arrays under the same comparator (csrc/clip_topk_key.inc); the two agree bit for
+ * bit.  No GPU needed.
+ * VG_ERR_ARG (nothing launched, outputs untouched): top_k < 1, top_k > VG_CLIP_MAX_TOPK, top_k > n_classes, n_classes < 1, null
+ * pointers with n > 0.  n <= 0 (with valid top_k / n_classes): VG_OK, nothing launched, nothing written. */
+#define VG_CLIP_MAX_TOPK 32
+int vg_clip_topk(const float* d_probs, int n, int n_classes, int top_k, int32_t* d_idx, float* d_score, void* stream);
+int vg_clip_topk_host(const float* h_probs, int n, int n_classes, int top_k, int32_t* h_idx, float* h_score);
 
 /* ---- ground segmentation (rows A1-A5) -----------------------------------------------------------
  * Replaces the pybind11 module `pypatchworkpp` (third_party/patchwork-plusplus/python_wrapper/pybinding.cpp:9-55)

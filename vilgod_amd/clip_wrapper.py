@@ -16,10 +16,35 @@ import numpy as np
 import torch
 
 from . import clip_weights
-from ._lib import lib, ptr, stream_ptr, check
+from ._lib import lib, ptr, stream_ptr, check, _DEFINES
 
 DTYPES = {'f32': 0, 'f16': 1}
 NARROW_CLASSES = 64          # vg_clip_scores' limit (one lane per class); longer class lists go to vg_clip_scores_wide
+MAX_TOPK = _DEFINES['CLIP_MAX_TOPK']         # vg_clip_topk's limit on clip.top_k
+
+
+def validate_top_k(top_k, n_classes=None):
+    """clip.top_k as the pipeline reads it: an integer 1 .. MAX_TOPK, and (where the class list is known) at most its length --
+    np.argpartition raises beyond it upstream (clip_utils.py:53).  Raises ValueError naming the key and the range; returns the int."""
+    if isinstance(top_k, (bool, np.bool_)) or not isinstance(top_k, (int, np.integer)) or not 1 <= top_k <= MAX_TOPK:
+        raise ValueError(f'clip.top_k must be an integer 1 .. {MAX_TOPK}, got {top_k!r}')
+    if n_classes is not None and top_k > n_classes:
+        raise ValueError(f'clip.top_k = {top_k} exceeds the {n_classes} classes of clip.class_list (1 .. {min(MAX_TOPK, n_classes)})')
+    return int(top_k)
+
+
+def clip_topk(probs, top_k, top=None, score=None, stream=None):
+    """The top_k classes of every row of `probs` [n, K] (CUDA float32, as clip_scores wrote it) -> (top [n, top_k] int32, score
+    [n, top_k] float32), best first (vg_clip_topk: probability descending, class index ascending).  `top` / `score`: buffers whose
+    first n rows are written instead of new tensors."""
+    n, K = probs.shape
+    assert probs.is_cuda and probs.dtype == torch.float32 and probs.is_contiguous()
+    if top is None:
+        top = torch.empty((n, top_k), dtype=torch.int32, device=probs.device)
+        score = torch.empty((n, top_k), dtype=torch.float32, device=probs.device)
+    assert top.is_contiguous() and score.is_contiguous() and top.shape[1] == top_k == score.shape[1] and len(top) >= n <= len(score)
+    check(lib.vg_clip_topk(ptr(probs), n, K, int(top_k), ptr(top), ptr(score), stream_ptr(stream)), 'vg_clip_topk')
+    return top[:n], score[:n]
 
 
 class VitEncoder:
@@ -125,7 +150,8 @@ class GraphClassifier:
                         # graph per exact count would be captured (~150 nodes + instantiate) for most frames.  The rows of the
                         # padding crops hold finite data of an earlier frame; their outputs are never read (<= 7 crops of ~330: ~1 %)
 
-    def __init__(self, encoder, text_features, max_crops=512, max_graphs=32, patch_width=256):
+    def __init__(self, encoder, text_features, max_crops=512, max_graphs=32, patch_width=256, top_k=1):
+        self.top_k = validate_top_k(top_k, text_features.shape[0])
         assert encoder.dtype == 'f16' and encoder.cfg['patch'] == 16 and encoder.cfg['resolution'] == 224 and patch_width in (256, 768)
         self.enc, self.text = encoder, text_features
         self.patch_width = int(patch_width)          # 256: single-channel rows (render 'patch16c1', input_kind 3); 768: 'patch16
@@ -153,6 +179,9 @@ class GraphClassifier:
         self.probs = torch.empty((self.cap, K), dtype=torch.float32, device=self.device)
         self.top1 = torch.empty((self.cap,), dtype=torch.int32, device=self.device)
         self.score = torch.empty((self.cap,), dtype=torch.float32, device=self.device)
+        if self.top_k > 1:          # vg_clip_topk's outputs (the graph keeps writing top1 / score above: its key and nodes are unchanged)
+            self.topk = torch.empty((self.cap, self.top_k), dtype=torch.int32, device=self.device)
+            self.topk_score = torch.empty((self.cap, self.top_k), dtype=torch.float32, device=self.device)
 
     def __del__(self):
         c = getattr(self, '_cache', None)
@@ -167,7 +196,8 @@ class GraphClassifier:
         return self.patches
 
     def classify(self, n, text_features=None):
-        """-> (probs [n,K], top1 [n], score [n]) views of the persistent outputs."""
+        """-> (probs [n,K], top1 [n], score [n]) views of the persistent outputs; with top_k > 1 top1 and score are [n, top_k], selected
+        by a plain vg_clip_topk launch on the same stream behind the graph's replay."""
         if text_features is not None and text_features is not self.text:
             assert text_features.shape == self.text.shape
             self.text = text_features                # (its pointer is part of the graph key: new features -> new graphs)
@@ -175,6 +205,9 @@ class GraphClassifier:
         check(lib.vg_vit_classify_graph(self.enc._h, self._cache, ptr(self.patches), 2 if self.patch_width == 768 else 3, nb, ptr(self.ws), ptr(self.feat), ptr(self.text),
                                         self.feat.shape[1], self.text.shape[0], ptr(self.probs), ptr(self.top1), ptr(self.score),
                                         stream_ptr()), 'vg_vit_classify_graph')
+        if self.top_k > 1:
+            top, score = clip_topk(self.probs[:n], self.top_k, self.topk, self.topk_score)
+            return self.probs[:n], top, score
         return self.probs[:n], self.top1[:n], self.score[:n]
 
     def stats(self):
@@ -183,8 +216,10 @@ class GraphClassifier:
         return {'graphs_captured': a.value, 'graph_launches': b.value, 'graphs_evicted': c.value, 'graphs_live': d.value}
 
 
-def clip_scores(feat, text_features, stream=None):
-    """-> (probs [n,K] f32, top1 [n] int32, top1_score [n] f32), clip_utils.py:42-61."""
+def clip_scores(feat, text_features, stream=None, top_k=1):
+    """-> (probs [n,K] f32, top1 [n] int32, top1_score [n] f32), clip_utils.py:42-61; with top_k > 1 top1 and top1_score are
+    [n, top_k], best first (vg_clip_topk on the same stream behind the scores)."""
+    top_k = validate_top_k(top_k, text_features.shape[0])
     n, dim = feat.shape
     K = text_features.shape[0]
     probs = torch.empty((n, K), dtype=torch.float32, device=feat.device)
@@ -194,6 +229,8 @@ def clip_scores(feat, text_features, stream=None):
         # one wave per crop up to its 64 classes, one workgroup per crop above (the same bits where both apply)
         fn, name = (lib.vg_clip_scores, 'vg_clip_scores') if K <= NARROW_CLASSES else (lib.vg_clip_scores_wide, 'vg_clip_scores_wide')
         check(fn(ptr(feat), n, dim, ptr(text_features), K, ptr(probs), ptr(top1), ptr(score), stream_ptr(stream)), name)
+    if top_k > 1:
+        top1, score = clip_topk(probs, top_k, stream=stream)
     return probs, top1, score
 
 
@@ -230,12 +267,11 @@ class ClipWrapper:
             device = 'cuda'
         self.device = torch.device(device)
         g = clip_cfg.get if hasattr(clip_cfg, 'get') else (lambda k, d=None: getattr(clip_cfg, k, d))
-        self.top_k = g('top_k', 1)
-        if self.top_k != 1:
-            raise NotImplementedError('only top_k = 1 (tools/configs/preprocessor/*.yaml) is implemented on the GPU')
+        self.top_k = validate_top_k(g('top_k', 1))
         self.split_size = g('split_size', 50)
         self.template = g('prompt_template')
         class_list = validate_class_list(g('class_list'), g('class_mapping'))       # before anything is built on the device
+        validate_top_k(self.top_k, len(class_list))
         self.id_to_class_dict = {idx: name for idx, name in enumerate(class_list)}
         model_name = str(g('model_name', 'ViT-B-16.pt'))
         tower = clip_weights.tower_config(model_name)        # raises for ViT-L-14-336px.pt; None for a name it does not know
@@ -295,13 +331,13 @@ class ClipWrapper:
 
     def predict_probs(self, crops, stream=None):
         feat = self.encoder.encode(crops, stream)
-        return clip_scores(feat, self.text_features, stream)
+        return clip_scores(feat, self.text_features, stream, top_k=self.top_k)
 
     def predict_clip_labels(self, crops):
-        """crops: [n,3,224,224] CUDA tensor.  Returns (class names, scores) lists of length n, as
-        clip_utils.py:49-63 with top_k = 1.  clip.class_list may have any length (clip_utils.py:22-26, 43): up to 64 classes are
+        """crops: [n,3,224,224] CUDA tensor.  Returns (class names, scores) lists of length n * top_k, as
+        clip_utils.py:49-63: crop-major, a crop's top_k entries best first.  clip.class_list may have any length (clip_utils.py:22-26, 43): up to 64 classes are
         scored by vg_clip_scores, longer lists by vg_clip_scores_wide."""
         probs, top1, score = self.predict_probs(crops)
-        top1 = top1.cpu().numpy()
-        score = score.cpu().numpy()
+        top1 = top1.cpu().numpy().reshape(-1)
+        score = score.cpu().numpy().reshape(-1)
         return [self.id_to_class_dict[int(i)] for i in top1], list(score)

@@ -156,11 +156,15 @@ def select_rows_device(d_index, d_seg, n_clusters, seg, keep):
 
 def vote(class_ids, scores, class_names_sorted):
     """LidarFrame.update_object_classes (lidar_frame.py:269-285) for all detections at once.
-    class_ids: [C,V] indices into `class_names_sorted` (ALPHABETICAL order = np.unique order); scores [C,V] float32.
+    class_ids: [C,V] indices into `class_names_sorted` (ALPHABETICAL order = np.unique order); scores [C,V] float32.  V counts every
+    entry of a detection: views x clip.top_k, view-major (what `cls_result_list.reshape((length, -1))` gives upstream).
     Returns (winner index [C], score [C] float32).
       no tie for the highest count -> that name (first in alphabetical order), mean score of its views
       tie -> the name with the highest mean score among ALL names present, scanned alphabetically with `>`
-             (max_score starts at 0)."""
+             (max_score starts at 0).
+    A name's mean is numpy's float32 np.mean of its entries in column order.  Below 8 entries that is the sequential sum formed
+    here for all rows at once; from 8 entries on numpy adds pairwise (eight accumulators, then the remainder), which no longer is
+    the sequential sum: those (row, name) pairs -- none unless V >= 8 -- get np.mean of the selection itself."""
     C, V = class_ids.shape
     K = len(class_names_sorted)
     counts = np.zeros((C, K), np.int64)
@@ -171,6 +175,10 @@ def vote(class_ids, scores, class_names_sorted):
         sums[np.arange(C), class_ids[:, v]] = cur + scores[:, v].astype(np.float32)
     with np.errstate(invalid='ignore', divide='ignore'):
         means = (sums / counts.astype(np.float32)).astype(np.float32)
+    if V >= 8:
+        sc32 = np.asarray(scores, np.float32)
+        for c, k in zip(*np.nonzero(counts >= 8)):
+            means[c, k] = np.mean(sc32[c][class_ids[c] == k])
     mx = counts.max(axis=1)
     tie = (counts == mx[:, None]).sum(axis=1) > 1
     win = counts.argmax(axis=1)                           # first maximum = alphabetical first

@@ -32,7 +32,7 @@ from . import patchworkpp as gpw
 from .hdbscan import HDBSCAN
 from .dbscan import DBSCAN, is_dbscan_target
 from .projection import RealisticProjection, VIEWS_4, VIEWS_6, check_image_size
-from .clip_wrapper import ClipWrapper
+from .clip_wrapper import ClipWrapper, validate_top_k
 
 # tools/configs/preprocessor/waymo.yaml:104-140
 DEFAULT_CLASS_LIST = ['car', 'truck', 'bus', 'van', 'minivan', 'pickup truck', 'school bus', 'fire truck', 'ambulance',
@@ -165,6 +165,8 @@ class PseudoLabelPipeline:
         # vg_clip_preprocess (projection.render_frame), others are refused here
         self.image_size = check_image_size(image_size)
         self._init_classes(clip_cfg)
+        if self.clip.top_k != self.top_k:
+            raise ValueError(f'clip.top_k = {self.top_k} in the configuration, but the ClipWrapper handed in was built with top_k = {self.clip.top_k}')
         self.class_names = list(_get(cfg, 'class_names', ['Vehicle', 'Pedestrian', 'Cyclist']))
         self.plane_seed = int(plane_seed)
         if box_mode not in ('reference', 'fast'):
@@ -204,6 +206,8 @@ class PseudoLabelPipeline:
     def _init_classes(self, clip_cfg):
         """The class tables of `vote_classes` from the clip node: fine classes, their mapped names, the key the results go under."""
         self.class_list = list(_get(clip_cfg, 'class_list'))
+        # clip.top_k: the entries per view that `classify` returns and `vote_classes` reads (clip_utils.py:53-61)
+        self.top_k = validate_top_k(_get(clip_cfg, 'top_k', 1), len(self.class_list))
         mapping = _get(clip_cfg, 'class_mapping')
         self.mapped_names = sorted(set(mapping[c] for c in self.class_list))          # alphabetical = np.unique order
         self.fine_to_mapped = np.array([self.mapped_names.index(mapping[c]) for c in self.class_list])
@@ -628,6 +632,8 @@ class PseudoLabelPipeline:
 
     # [D1]-[D9]
     def classify(self, d_X, d_index, d_seg, transform_to_ego, image_size=None):
+        """-> (probs [n, K], top1, score) on the device, n = clusters x views.  clip.top_k = 1: top1 and score are [n]; above, [n, top_k]
+        with a crop's entries best first (vg_clip_topk behind the scores on the same stream) -- `vote_classes` takes either."""
         n = (d_seg.numel() - 1) * self.projection.num_views
         size = self.image_size if image_size is None else image_size      # (a stage's own `image_size` argument overrides the pipeline's)
         enc = self.clip.encoder
@@ -641,7 +647,8 @@ class PseudoLabelPipeline:
                 # captured loop: the ViT encode + scores replay as one hipGraph (per crop count) on this worker's persistent buffers;
                 # the outputs are cloned because the buffers are rewritten by the worker's next frame
                 if self._graph_cls is None:
-                    self._graph_cls = GraphClassifier(enc, self.clip.text_features, max_crops=max(512, n), patch_width=256 if self.patch_1ch else 768)
+                    self._graph_cls = GraphClassifier(enc, self.clip.text_features, max_crops=max(512, n), patch_width=256 if self.patch_1ch else 768,
+                                                      top_k=self.top_k)
                 g = self._graph_cls
                 self.projection.render_frame(d_X, d_index, d_seg, transform_to_ego, out=pmode, out_buf=g.patch_buffer(n), image_size=size)
                 with self._vit_in_turn():
@@ -649,7 +656,8 @@ class PseudoLabelPipeline:
                 return probs.clone(), top1.clone(), score.clone()
             patches = self.projection.render_frame(d_X, d_index, d_seg, transform_to_ego, out=pmode, image_size=size)
             self._mark('render')
-            return self._on_vit_stream(lambda: clip_scores(enc.encode_patches(patches, n), self.clip.text_features), patches, n)
+            return self._on_vit_stream(lambda: clip_scores(enc.encode_patches(patches, n), self.clip.text_features, top_k=self.top_k),
+                                       patches, n)
         crops = self.projection.render_frame(d_X, d_index, d_seg, transform_to_ego, out='f16' if self.vit_dtype == 'f16' else 'f32', image_size=size)
         if enc.cfg['patch'] == 16:
             return self.clip.predict_probs(crops)
@@ -1038,9 +1046,10 @@ class PseudoLabelPipeline:
         return valid, stats
 
     def vote_classes(self, fs, key, which, top1, score):
-        """[D10]: the views' top-1 fine classes and scores (host, one row of `num_views` per True entry of `which`) -> mapped names,
-        vote, fs.set_classes(key, ...).  -> (names: the mapped names as an object array, win [rows] indices into it, final [rows])."""
-        V = self.projection.num_views
+        """[D10]: the views' top-k fine classes and scores (host, one row of `num_views * clip.top_k` per True entry of `which`:
+        view-major, a view's entries best first, as `classify` returns them) -> mapped names, vote, fs.set_classes(key, ...).
+        -> (names: the mapped names as an object array, win [rows] indices into it, final [rows])."""
+        V = self.projection.num_views * self.top_k
         fine = top1.reshape(-1, V)
         sc = score.reshape(-1, V).astype(np.float32)
         mapped = self.fine_to_mapped[fine]
