@@ -431,6 +431,9 @@ typedef struct vg_cluster vg_cluster;
 #define VG_CLUSTER_MAX_K 64 /* largest min_samples of vg_cluster_mst[_nd] */
 int vg_cluster_create(vg_cluster** out, int max_points);
 void vg_cluster_destroy(vg_cluster* h);
+/* HOST ONLY (no HIP call): bytes of device memory a handle for max_points points holds in its listed buffers (csrc/cluster.hip
+ * CL_BUFFERS) -- all of it but the sort / scan scratch, a few MB.  0 for max_points <= 0. */
+size_t vg_cluster_bytes(int max_points);
 /* d_points [n,stride] f32 (x,y,z first; `points_ref_wo_ground[..., :3]`, zero_shot_detector.py:246).
  * k = min_samples (= min_cluster_size in the reference's configuration), 1 <= k <= VG_CLUSTER_MAX_K (VG_ERR_ARG outside):
  * core distance = distance to the k-th nearest OTHER point, +inf for a point with fewer than k others.  k <= 15 keeps each

@@ -1,4 +1,4 @@
-"""Inputs, a plain round counter and the grid-geometry probe for the Boruvka MST of csrc/cluster.hip.  TEST INFRASTRUCTURE ONLY.
+"""Inputs, a plain round counter and the grid-geometry probe for the Boruvka MST of csrc/cluster_mst.inc (geometry: cluster_geom.inc).  TEST INFRASTRUCTURE ONLY.
 
 Three things live here:
   * `probe`: the host-only C entry vg_cluster_geom_probe -- the origin, cells, Morton codes, box distances and shell radii the kernels

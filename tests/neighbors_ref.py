@@ -1,4 +1,4 @@
-"""Dense references and input families for the fixed-radius neighbour queries (csrc/cluster.hip: k_cl_ball_count, k_cl_nearest), the
+"""Dense references and input families for the fixed-radius neighbour queries (csrc/cluster_queries.inc: k_cl_ball_count, k_cl_nearest), the
 entropy score (csrc/segment.hip: k_entropy_scores) and the subsample keys (k_subsample_keys).  TEST INFRASTRUCTURE ONLY.
 
 The references work on ALL query x target pairs in chunks: no KD-tree, no cells, no pruning, so nothing a pruning rule can get wrong

@@ -1,5 +1,5 @@
 """`min_samples` (and with it `clustering.model.min_cluster_size`) above 15: exact core distances for 16 <= k <= 64 on the GPU
-(csrc/cluster.hip: k_cl_core_blk with its LDS-heap list and the wave-wide form of k_cl_core_far), through the C ABI, `HDBSCAN`, the fused pipeline and the CLI.
+(csrc/cluster_core.inc: k_cl_core_blk with its LDS-heap list and the wave-wide form of k_cl_core_far), through the C ABI, `HDBSCAN`, the fused pipeline and the CLI.
 
 CPU: the oracle stays pinned to scikit-learn for the new range (MST weights bit-identical, tree stages equal on the same linkage);
 the header's VG_CLUSTER_MAX_K.  GPU: squared core distances, MST, labels and probabilities equal to the oracle bit for bit.

@@ -1,4 +1,4 @@
-"""The Boruvka MST of csrc/cluster.hip at its edges: the geometry its walks prune with (CPU, through vg_cluster_geom_probe, on the
+"""The Boruvka MST of csrc/cluster_mst.inc (geometry: cluster_geom.inc) at its edges: the geometry its walks prune with (CPU, through vg_cluster_geom_probe, on the
 shipped source) and scenes aimed at each pruning rule (GPU, exact against the oracle).
 
 CPU part.  The walk skips a node when its box distance exceeds the best candidate, so the box distance has to be a LOWER BOUND of the

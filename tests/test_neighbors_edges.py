@@ -1,4 +1,4 @@
-"""The fixed-radius neighbour queries (csrc/cluster.hip: k_cl_ball_count, k_cl_nearest through vg_cluster_grid / _ball_count /
+"""The fixed-radius neighbour queries (csrc/cluster_queries.inc: k_cl_ball_count, k_cl_nearest through vg_cluster_grid / _ball_count /
 _nearest), the entropy score and the subsample keys (csrc/segment.hip: k_entropy_scores, k_subsample_keys) at their edges: pairs
 exactly at the radius across cell faces, edges and corners, near the origin and 1 km from it; queries outside the grid and clamped
 targets; equidistant targets in different cells; the cap; reach 8 and its refusal; block and stride shapes; the pairwise summation

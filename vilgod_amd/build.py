@@ -154,7 +154,7 @@ def check_w4_epilogues():
 
 
 def check_isa(sources=None, verbose=False):
-    """Guard against a code-generation bug of this ROCm's gfx950 back end (found in round 3, csrc/cluster.hip ClGrid::inf): a
+    """Guard against a code-generation bug of this ROCm's gfx950 back end (found in round 3, csrc/cluster_geom.inc ClGrid::inf): a
     wave-uniform 64-bit constant whose HIGH half is not zero -- `double x = INFINITY` kept in SGPRs -- can be materialised as
     `s_mov_b64 s[..], 0x7ff0000000000000`.  gfx9 encodes 32-bit literals only: the assembler rejects that line, and the direct
     object emission drops the high half (the kernel then sees 0.0).  Compiles the sources to assembly (device side only) and

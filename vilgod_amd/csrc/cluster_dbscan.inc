@@ -1,5 +1,5 @@
 // DBSCAN on the handle's cell grid: vg_cluster_dbscan / vg_dbscan_host (included by cluster.hip, which owns the grid, its sorted point
-// copy, cl_box_d2 and the rocprim scratch this file uses).
+// copy, cl_box_d2, the rocprim scratch this file uses, and the working arrays it borrows: ClDbscanView).
 //
 // sklearn.cluster.DBSCAN, the second model the reference's cluster_utils.py imports (src/utils/cluster_utils.py:4-5), as the rules
 // its `dbscan_inner` computes, stated without its traversal (include/vilgod_hip.h has the contract):
@@ -27,7 +27,6 @@
 // whole slab or row of cells whose own gap already exceeds eps2 is skipped before its cells are formed.
 
 #define DB_NT 256
-#define DB_STATUS 8                   // word of vg_cluster::d_counter: not 0 = a bounded walk or retry loop overran (cannot happen)
 
 template <int DIM>
 __device__ __forceinline__ DbRow db_row(const float4* __restrict__ spts, const float* __restrict__ st, int j) {
@@ -215,27 +214,19 @@ static int db_run(vg_cluster* h, const float* d_points, int n, int stride, int s
         const int rc = cl_build_grid(h, d_points, n, stride, DIM, st, true);
         if (rc != VG_OK) return rc;
     }
-    // the working arrays: the Boruvka stage's, [max_points] each (an MST on this handle initialises every one it reads)
-    int* const core = h->d_comp;
-    int* const parent = h->d_parent2;
-    int* const minrow = h->d_csize;
-    int* const flag = h->d_sel_a;
-    int* const scan = h->d_sel_b;
-    int* const root = h->d_mst_a;
-    int* const label_s = h->d_pt_b;
-    int* const status = h->d_counter + DB_STATUS;
+    const ClDbscanView v = cl_dbscan_view(h);         // the working arrays, [max_points] each
     const dim3 grid(vg_div_up(n, DB_NT)), block(DB_NT);
     hipLaunchKernelGGL((k_db_core<DIM>), grid, block, 0, st, h->d_spts, h->d_st, n, h->d_grid, h->d_cell_start, h->d_perm, span, eps2,
-                       min_samples, core, parent, minrow, flag, status);
-    hipLaunchKernelGGL((k_db_union<DIM>), grid, block, 0, st, h->d_spts, h->d_st, n, h->d_grid, h->d_cell_start, span, eps2, core, parent,
-                       status);
-    hipLaunchKernelGGL(k_db_roots, grid, block, 0, st, n, core, h->d_perm, parent, root, minrow, status);
-    hipLaunchKernelGGL(k_db_mark, grid, block, 0, st, n, root, h->d_perm, minrow, flag);
+                       min_samples, v.core, v.parent, v.minrow, v.flag, v.status);
+    hipLaunchKernelGGL((k_db_union<DIM>), grid, block, 0, st, h->d_spts, h->d_st, n, h->d_grid, h->d_cell_start, span, eps2, v.core, v.parent,
+                       v.status);
+    hipLaunchKernelGGL(k_db_roots, grid, block, 0, st, n, v.core, h->d_perm, v.parent, v.root, v.minrow, v.status);
+    hipLaunchKernelGGL(k_db_mark, grid, block, 0, st, n, v.root, h->d_perm, v.minrow, v.flag);
     size_t tb = h->temp_bytes;
-    VG_CHECK(rocprim::exclusive_scan(h->d_temp, tb, flag, scan, 0, (size_t)n, rocprim::plus<int>(), st));
-    hipLaunchKernelGGL(k_db_label, grid, block, 0, st, n, root, minrow, flag, scan, status, label_s, d_n_clusters);
+    VG_CHECK(rocprim::exclusive_scan(h->d_temp, tb, v.flag, v.scan, 0, (size_t)n, rocprim::plus<int>(), st));
+    hipLaunchKernelGGL(k_db_label, grid, block, 0, st, n, v.root, v.minrow, v.flag, v.scan, v.status, v.label_s, d_n_clusters);
     hipLaunchKernelGGL((k_db_border<DIM>), grid, block, 0, st, h->d_spts, h->d_st, n, h->d_grid, h->d_cell_start, h->d_perm, span, eps2,
-                       core, label_s, d_labels, d_core, d_probs);
+                       v.core, v.label_s, d_labels, d_core, d_probs);
     VG_LAUNCH_CHECK();
     return VG_OK;
 }

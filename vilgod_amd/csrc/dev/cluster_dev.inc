@@ -104,7 +104,7 @@ __global__ void k_cl_seedsim_drop(int n, const double* __restrict__ core2, const
     const int a = blockIdx.x * blockDim.x + threadIdx.x;
     if (a >= n) return;
     const bool seedable = pt_b[a] >= 0 && pt_w[a] == (unsigned long long)__double_as_longlong(core2[a]);
-    if (!seedable) { pt_b[a] = -1; atomicAdd(&counter[5], 1); }
+    if (!seedable) { pt_b[a] = -1; atomicAdd(&counter[CL_CNT_DEV], 1); }
 }
 
 // sit_min, xcd_order and first_batch are read HERE, once per MST, and handed to every launch of every round (ADVICE r5: a switch that a
@@ -162,14 +162,14 @@ static void cl_dev_round_search(vg_cluster* h, int n, hipStream_t st, int r, con
     }
     cl_dev_launch_walk<DIM>(h, n, st, sw);
     if (r == 1 && getenv("VG_CLUSTER_SEEDSIM")) {
-        (void)hipMemsetAsync(h->d_counter + 5, 0, 4, st);
+        (void)hipMemsetAsync(h->d_counter + CL_CNT_DEV, 0, 4, st);
         hipLaunchKernelGGL(k_cl_seedsim_drop, dim3(nb), dim3(256), 0, st, n, h->d_core2, h->d_pt_w, h->d_pt_b, h->d_counter);
         hipLaunchKernelGGL(k_cl_b_round_init, dim3(nb), dim3(256), 0, st, n, h->d_comp, h->d_best_w, h->d_best_d, h->d_best_e, h->d_sel_a, flags, h->d_csize, h->d_giant, h->d_code_s, h->d_cell_comp);
         hipLaunchKernelGGL(k_cl_b_seed, dim3(nb), dim3(256), 0, st, n, h->d_comp, h->d_pt_b, h->d_pt_w, h->d_best_w, flags);
         hipLaunchKernelGGL(k_cl_b_purity, dim3(nb), dim3(256), 0, st, n, h->d_code_s, h->d_comp, h->d_cell_comp, flags);   // (round_init rewrote the pure values)
         cl_dev_launch_walk<DIM>(h, n, st, sw);          // walks only the points that were not seedable
         int left = 0;
-        (void)hipMemcpyAsync(&left, h->d_counter + 5, 4, hipMemcpyDeviceToHost, st);
+        (void)hipMemcpyAsync(&left, h->d_counter + CL_CNT_DEV, 4, hipMemcpyDeviceToHost, st);
         (void)hipStreamSynchronize(st);
         fprintf(stderr, "[cluster seedsim] round 1: %d of %d points have no edge at their own core distance (the second k_cl_b_search launch walks only these)\n", left, n);
     }

@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from ._lib import lib, ptr, stream_ptr, check
-from .hdbscan import GridQueries
+from .cluster_handle import GridQueries
 
 EPS_CELL, EPS_MAX_REACH = 0.4, 8
 
@@ -28,6 +28,7 @@ EPS_CELL, EPS_MAX_REACH = 0.4, 8
 class DBSCAN(GridQueries):
     def __init__(self, eps=0.5, min_samples=5, metric='euclidean', metric_params=None, algorithm='auto', leaf_size=30, p=None,
                  n_jobs=None, max_points=400_000, device='cuda', **unused):
+        """max_points: the largest point set `fit` / `labels_device` take; the handle holds `cluster_handle.HANDLE_COST` for it."""
         for k in unused:
             raise TypeError(f'unexpected keyword {k}')
         if metric != 'euclidean' or metric_params:
@@ -43,7 +44,7 @@ class DBSCAN(GridQueries):
         self.device = torch.device(device)
         self.max_points = int(max_points)
         self.hierarchy = None                    # no hierarchy stage (what TwoFrameClusterer and the pipeline look at)
-        self._create_handle()
+        GridQueries.__init__(self, self.max_points, self.device)
         self.labels_ = None
         self.core_sample_indices_ = None
         self.components_ = None

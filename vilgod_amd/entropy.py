@@ -8,7 +8,7 @@ Mirrors
   pointcloud_utils.knn_labels   src/utils/pointcloud_utils.py:505-513
 
 All neighbour searches run on the GPU through the cell grid of a `vilgod_amd.hdbscan.HDBSCAN` handle
-(csrc/cluster.hip: vg_cluster_grid / vg_cluster_ball_count / vg_cluster_nearest); the scores come from
+(csrc/cluster.hip, cluster_queries.inc: vg_cluster_grid / vg_cluster_ball_count / vg_cluster_nearest); the scores come from
 vg_entropy_scores, the random half-sample from vg_subsample_keys (counter-based; the reference draws from numpy's global
 Mersenne state, which no implementation can reproduce).
 """

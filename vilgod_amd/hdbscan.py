@@ -3,7 +3,7 @@
 min_cluster_size=15, metric='euclidean', core_dist_n_jobs=-1)`; `.fit(X)` then `.labels_`,
 `.probabilities_`, src/vilgod/zero_shot_detector.py:248-250), running on the GPU:
 
-    core distances + exact mutual-reachability MST + edge sort   csrc/cluster.hip   (GPU)
+    core distances + exact mutual-reachability MST + edge sort   csrc/cluster.hip: cluster_core.inc, cluster_mst.inc   (GPU)
     single linkage / condense / selection / epsilon / labels     csrc/hdbscan_tree.cpp (host, C++), or -- `hierarchy='device'` --
                                                                  csrc/hdbscan_device.hip (GPU, the same results bit for bit)
 
@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from ._lib import lib, ptr, stream_ptr, check, CLUSTER_MAX_K
+from .cluster_handle import GridQueries      # noqa: F401  (the base of HDBSCAN; importable from here too)
 
 
 def selection_options(cluster_selection_method='eom', allow_single_cluster=False, max_cluster_size=None):
@@ -31,73 +32,11 @@ def selection_options(cluster_selection_method='eom', allow_single_cluster=False
     return (1 if cluster_selection_method == 'leaf' else 0, int(bool(allow_single_cluster)), int(max_cluster_size) if max_cluster_size else 0)
 
 
-class GridQueries:
-    """What every clustering model of this package owns and offers besides its clustering: a `vg_cluster` handle (`self._h`, for up to
-    `self.max_points` points on `self.device`) and the queries on its cell grid that `EntropyScorer`, `TwoFrameClusterer` and
-    `vilgod_amd.knn` call on the pipeline's model."""
-
-    def _create_handle(self):
-        h = ctypes.c_void_p()
-        with torch.cuda.device(self.device):
-            check(lib.vg_cluster_create(ctypes.byref(h), self.max_points), 'vg_cluster_create')
-        self._h = h
-
-    def __del__(self):
-        h = getattr(self, '_h', None)
-        if h is not None and lib is not None:
-            lib.vg_cluster_destroy(h)
-            self._h = None
-
-    # ---- fixed-radius queries on the same cell grid (SURVEY 8f N1) -----------------------------------
-    def grid(self, T, stream=None):
-        """Build the handle's cell grid over target points T (CUDA float32 [n,>=3]); valid until the next grid()/mst()."""
-        assert T.is_cuda and T.dtype == torch.float32 and (T.shape[0] == 0 or T.stride(1) == 1)
-        check(lib.vg_cluster_grid(self._h, ptr(T), T.shape[0], T.stride(0) if T.shape[0] else 3, stream_ptr(stream)),
-              'vg_cluster_grid')
-        self._grid_ref = T                      # the kernels read the handle's own sorted copy; kept for clarity only
-
-    def ball_count(self, Q, r2, cap, out=None, stream=None):
-        """-> int32 [nq]: min(cap, #{grid points with float32 d2 < r2}) per query row of Q (CUDA float32 [nq,>=3])."""
-        assert Q.is_cuda and Q.dtype == torch.float32 and (Q.shape[0] == 0 or Q.stride(1) == 1)
-        nq = Q.shape[0]
-        if out is None:
-            out = torch.empty(nq, dtype=torch.int32, device=Q.device)
-        check(lib.vg_cluster_ball_count(self._h, ptr(Q), nq, Q.stride(0) if nq else 3, float(np.float32(r2)), int(cap), ptr(out),
-                                        stream_ptr(stream)), 'vg_cluster_ball_count')
-        return out
-
-    def nearest(self, Q, max_d2, stream=None):
-        """-> (idx int32 [nq] row of the grid's point array or -1, d2 float32 [nq]) of the nearest grid point with
-        float32 d2 <= max_d2."""
-        assert Q.is_cuda and Q.dtype == torch.float32 and (Q.shape[0] == 0 or Q.stride(1) == 1)
-        nq = Q.shape[0]
-        idx = torch.empty(nq, dtype=torch.int32, device=Q.device)
-        d2 = torch.empty(nq, dtype=torch.float32, device=Q.device)
-        check(lib.vg_cluster_nearest(self._h, ptr(Q), nq, Q.stride(0) if nq else 3, float(np.float32(max_d2)), ptr(idx), ptr(d2),
-                                     stream_ptr(stream)), 'vg_cluster_nearest')
-        return idx, d2
-
-    def knn(self, Q, K, max_d2=float('inf'), out=None, stream=None):
-        """-> (idx int32 [nq,K] rows of the grid's point array, d2 float32 [nq,K]): per query row of Q (CUDA float32 [nq,>=3]) the K
-        grid points with the smallest (float32 d2, row) among those with d2 <= max_d2, in that order; -1 / +inf where there are fewer,
-        and in a whole row whose query is not finite (vg_cluster_knn: no radius limit, one launch).  out: an (idx, d2) pair to write."""
-        assert Q.is_cuda and Q.dtype == torch.float32 and (Q.shape[0] == 0 or Q.stride(1) == 1)
-        nq, K = Q.shape[0], int(K)
-        if out is None:
-            out = (torch.empty((nq, max(K, 0)), dtype=torch.int32, device=Q.device),
-                   torch.empty((nq, max(K, 0)), dtype=torch.float32, device=Q.device))
-        idx, d2 = out
-        assert idx.dtype == torch.int32 and d2.dtype == torch.float32 and idx.shape == d2.shape == (nq, K)
-        assert idx.is_contiguous() and d2.is_contiguous() and idx.device == d2.device == Q.device
-        check(lib.vg_cluster_knn(self._h, ptr(Q), nq, Q.stride(0) if nq else 3, K, float(np.float32(max_d2)), ptr(idx), ptr(d2),
-                                 stream_ptr(stream)), 'vg_cluster_knn')
-        return idx, d2
-
-
 class HDBSCAN(GridQueries):
     def __init__(self, min_cluster_size=5, min_samples=None, cluster_selection_epsilon=0.0, metric='euclidean',
                  core_dist_n_jobs=None, max_points=400_000, device='cuda', hierarchy='host', cluster_selection_method='eom',
                  allow_single_cluster=False, max_cluster_size=None, **unused):
+        """max_points: the largest point set `fit` / `mst` take; the handle holds `cluster_handle.HANDLE_COST` for it."""
         if metric != 'euclidean':
             raise NotImplementedError('only the euclidean metric of the reference configuration is implemented')
         for k in unused:
@@ -124,7 +63,7 @@ class HDBSCAN(GridQueries):
             hierarchy = 'host'
         self.hierarchy = hierarchy
         self._hier = None
-        self._create_handle()
+        GridQueries.__init__(self, self.max_points, self.device)
         self.labels_ = None
         self.probabilities_ = None
         self.n_rounds_ = 0

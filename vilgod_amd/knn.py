@@ -28,7 +28,7 @@ KNN_SWITCH_K = tuple(_DEFINES[k] for k in ('KNN_K_REG1', 'KNN_K_REG4', 'KNN_K_RE
 KNN = collections.namedtuple('KNN', 'dists idx knn')       # pytorch3d.ops.knn._KNN
 
 _MIN_HANDLE_POINTS = 1 << 16
-_handles = {}                                              # device index -> HDBSCAN used for its grid only
+_handles = {}                                              # device index -> GridQueries
 
 
 def _np_ptr(a):
@@ -36,14 +36,15 @@ def _np_ptr(a):
 
 
 def _handle(device, n_targets):
-    """The cached grid handle of `device`, replaced by a larger one when `n_targets` does not fit."""
-    from .hdbscan import HDBSCAN
+    """The cached grid handle of `device`, replaced by a larger one when `n_targets` does not fit.  A full handle, of which the search
+    uses the grid buffers only: `cluster_handle.HANDLE_COST` for its max_points (at least _MIN_HANDLE_POINTS, doubled when it grows)."""
+    from .cluster_handle import GridQueries
     h = _handles.get(device.index)
     if h is None or h.max_points < n_targets:
         grow = 0 if h is None else 2 * h.max_points
         _handles.pop(device.index, None)                   # (the old handle's buffers go before the new ones come)
         del h
-        h = _handles[device.index] = HDBSCAN(max_points=max(n_targets, grow, _MIN_HANDLE_POINTS), device=device)
+        h = _handles[device.index] = GridQueries(max(n_targets, grow, _MIN_HANDLE_POINTS), device)
     return h
 
 
@@ -63,7 +64,7 @@ def knn_points(p1, p2, lengths1=None, lengths2=None, K=1, norm=2, version=-1, re
     are -1 / +inf (`knn`: zeros) -- see the module docstring.  `version` and `return_sorted` are accepted and change nothing: there is
     one kernel and its output is always sorted.  One vg_cluster_grid plus one vg_cluster_knn per batch element; the queries are sent
     in `entropy.spatial_order` (neighbouring lanes walk neighbouring nodes) and put back.
-    model: an `HDBSCAN` whose grid handle is used (its grid is overwritten); default: one cached handle per device."""
+    model: a `GridQueries` (an `HDBSCAN`, say) whose grid handle is used (its grid is overwritten); default: one cached handle per device."""
     import torch
     from .entropy import spatial_order
     if norm != 2:

@@ -6,7 +6,7 @@ benchmark can call them one by one; `process_frame` chains them.
 
     ground(points)                 A1-A5   csrc/ground.hip
     to_ref + non-ground gather     B1      csrc/segment.hip (+ torch index plumbing)
-    cluster(X)                     B2-B3   csrc/cluster.hip (GPU) + csrc/hdbscan_tree.cpp (host)
+    cluster(X)                     B2-B3   csrc/cluster.hip + cluster_*.inc (GPU) + csrc/hdbscan_tree.cpp (host)
     cluster packing                B3      csrc/hdbscan_tree.cpp (host; default) or csrc/pack.hip (GPU, pack='device')
     ground plane + filters         C1-C2   csrc/segment.hip
     render + encode + score        D1-D9   csrc/render.hip, csrc/vit.hip
