@@ -454,7 +454,9 @@ int vg_cluster_mst_nd(vg_cluster* h, const float* d_points, int n, int stride, i
 
 /* ---- fixed-radius neighbour queries (entropy scores, two-frame clustering) -------------------
  * vg_cluster_grid builds the handle's 0.4 m cell grid over a TARGET set; it stays valid until the next
- * vg_cluster_grid / vg_cluster_mst[_nd] call on the handle. */
+ * vg_cluster_grid / vg_cluster_mst[_nd] call on the handle.  Queued on `stream`: nothing is read back and nothing is copied from
+ * the host, so the call can be captured into a graph (the number of targets is the handle's host state: a replay serves the n of
+ * the captured call). */
 int vg_cluster_grid(vg_cluster* h, const float* d_points, int n, int stride, void* stream);
 /* d_counts[i] = min(cap, #{target t : d2(query_i, t) < r2}) with float32 d2 = fma(dz,dz,fma(dy,dy,dx*dx)):
  * what pointcloud_utils.py:74-107 derives from pcdet's ball_query (r2 = float32(radius)^2; count_neighbors: radius
@@ -502,6 +504,37 @@ int vg_knn_host(const float* h_query, int nq, int qstride, const float* h_target
  * (vg_cluster_geom_probe h_box_d2) is box_d2: a lower bound of the FLOAT32 d2 to every target of the node.  The walk skips the node
  * only when this value is strictly greater. */
 double vg_knn_prune_bound_host(double box_d2);
+
+/* ---- ball query, the index form of vg_cluster_ball_count (csrc/cluster_ball_query.inc) ------------------------
+ * pcdet's `pcdet.ops.pointnet2.pointnet2_stack.pointnet2_utils.ball_query` (ball_query_kernel_stack plus its Python wrapper) as the
+ * reference calls it: pointcloud_utils.py:83 (count_neighbors) and :99 (count_neighbors_inter_frame).
+ *   targets        the point set last given to vg_cluster_grid on h (or to vg_cluster_mst[_nd] / vg_cluster_dbscan); a target's row is
+ *                  its index in that array
+ *   hits           H(q) = the target rows t with cl_d2_f32(q, t) < r2, STRICTLY; cl_d2_f32 is the float32
+ *                  fmaf(dz, dz, fmaf(dy, dy, dx * dx)) of vg_cluster_ball_count / _nearest / _knn (ONE function, called by the kernel
+ *                  and by vg_ball_query_host).  A query that is itself a target is a hit.
+ *   outputs        cnt(q) = min(|H(q)|, nsample); d_idx[q, 0 .. cnt) = the cnt SMALLEST rows of H(q), ascending (pcdet walks the
+ *                  targets in row order and keeps the first nsample hits); d_idx[q, cnt .. nsample) = d_idx[q, 0], pcdet's padding
+ *                  with the first hit; an empty ball: cnt = 0 and a row of zeros (what pcdet's wrapper leaves after
+ *                  idx[empty_ball_mask] = 0).  d_idx int32 [nq, nsample]; d_cnt int32 [nq], may be NULL.
+ *   not finite     a query row with a coordinate that is not finite has an empty ball (decided before any cell is indexed); a target
+ *                  with such a coordinate is never a hit.  Both are what pcdet's arithmetic gives.
+ *   consequence    cnt equals vg_cluster_ball_count(..., cap = nsample) for every query.
+ *   refusals       VG_ERR_ARG, nothing launched, outputs untouched: r2 NaN or <= 0; ceil(sqrt(r2) / 0.4) > 8 (the grid's reach limit,
+ *                  3.2 m, as vg_cluster_ball_count); nsample < 1 or > VG_BALL_QUERY_MAX_NSAMPLE (the reference uses 1000 and 100);
+ *                  qstride < 3; null h, d_query or d_idx with nq > 0.  nq == 0 is VG_OK.  An empty grid gives zeros and cnt = 0.
+ * One launch on `stream`, its grid sized from nq alone: nothing read back, nothing allocated, no global-memory atomics, capturable;
+ * the same bits on every run.  One wave per query collects the hits' rows in an LDS buffer of VG_BALL_QUERY_CAND entries; before the
+ * buffer could overflow it is sorted, the nsample smallest rows stay and only hits below the largest of them are taken from then on.
+ * All scratch is LDS: the handle holds no buffer for this call. */
+#define VG_BALL_QUERY_MAX_NSAMPLE 1024
+#define VG_BALL_QUERY_CAND 2048
+int vg_cluster_ball_query(vg_cluster* h, const float* d_query, int nq, int qstride, float r2, int nsample, int32_t* d_idx,
+                          int32_t* d_cnt, void* stream);
+/* HOST ONLY, no GPU: pcdet's loop as written -- the targets [n, tstride] in row order, the first nsample hits, the same pair function,
+ * the same outputs (cnt may be NULL).  No reach limit; the other refusals as above (tstride < 3: VG_ERR_ARG). */
+int vg_ball_query_host(const float* targets, int n, int tstride, const float* query, int nq, int qstride, float r2, int nsample,
+                       int32_t* idx, int32_t* cnt);
 
 /* DBSCAN: sklearn.cluster.DBSCAN, the second clustering model the reference's cluster_utils.py imports (src/utils/cluster_utils.py:4-5),
  * on the handle's 0.4 m grid (csrc/cluster_dbscan.inc).  The definition -- what sklearn's dbscan_inner computes, stated without its

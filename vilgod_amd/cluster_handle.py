@@ -52,6 +52,23 @@ class GridQueries:
                                         stream_ptr(stream)), 'vg_cluster_ball_count')
         return out
 
+    def ball_query(self, Q, r2, nsample, out=None, stream=None):
+        """-> (idx int32 [nq,nsample], cnt int32 [nq]): per query row of Q (CUDA float32 [nq,>=3]) the min(hits, nsample) LOWEST rows of
+        the grid's point array with float32 d2 < r2, ascending, then the first of them repeated; a row of zeros and cnt 0 for an empty
+        ball and for a query that is not finite (vg_cluster_ball_query: pcdet's ball_query, one launch).  cnt equals
+        ball_count(Q, r2, nsample).  out: an (idx, cnt) pair to write."""
+        assert Q.is_cuda and Q.dtype == torch.float32 and (Q.shape[0] == 0 or Q.stride(1) == 1)
+        nq, nsample = Q.shape[0], int(nsample)
+        if out is None:
+            out = (torch.empty((nq, max(nsample, 0)), dtype=torch.int32, device=Q.device),
+                   torch.empty(nq, dtype=torch.int32, device=Q.device))
+        idx, cnt = out
+        assert idx.dtype == cnt.dtype == torch.int32 and idx.shape == (nq, nsample) and cnt.shape == (nq,)
+        assert idx.is_contiguous() and cnt.is_contiguous() and idx.device == cnt.device == Q.device
+        check(lib.vg_cluster_ball_query(self._h, ptr(Q), nq, Q.stride(0) if nq else 3, float(np.float32(r2)), nsample, ptr(idx), ptr(cnt),
+                                        stream_ptr(stream)), 'vg_cluster_ball_query')
+        return idx, cnt
+
     def nearest(self, Q, max_d2, stream=None):
         """-> (idx int32 [nq] row of the grid's point array or -1, d2 float32 [nq]) of the nearest grid point with
         float32 d2 <= max_d2."""

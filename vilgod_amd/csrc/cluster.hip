@@ -23,6 +23,7 @@
 //                        cooperative phases replaced, and the A/B switches.
 //   cluster_queries.inc  beside the clustering, on the same grid over a TARGET set (vg_cluster_grid): the fixed-radius queries
 //                        k_cl_ball_count / k_cl_nearest
+//   cluster_ball_query.inc  ... the rows of the targets inside the radius (pcdet's ball_query), k_cl_ball_query: one wave per query
 //   cluster_knn.inc      ... and the K nearest targets without a radius, k_cl_knn
 //   cluster_dbscan.inc   DBSCAN, the reference's other clustering model, on the same grid: k_db_* (with dbscan_pair.inc)
 // This file: the handle -- the counter words (ClCounter), THE list of its buffers (CL_BUFFERS), the buffers DBSCAN borrows
@@ -173,7 +174,8 @@ static int cl_with_dim(int dim, Body&& body) {
 #include "cluster_core.inc"
 #include "cluster_mst.inc"
 #include "cluster_queries.inc"
-#include "cluster_knn.inc"      // K nearest targets, no radius limit: k_cl_knn, vg_cluster_knn, vg_knn_host
+#include "cluster_ball_query.inc"      // the rows inside the radius, pcdet's ball_query: k_cl_ball_query, vg_cluster_ball_query, vg_ball_query_host
+#include "cluster_knn.inc"     // K nearest targets, no radius limit: k_cl_knn, vg_cluster_knn, vg_knn_host
 
 // every buffer of a handle whose members are all null (vg_cluster_create frees what is there when this fails half-way)
 static int cl_alloc(vg_cluster* h) {
@@ -236,7 +238,9 @@ int vg_cluster_grid(vg_cluster* h, const float* d_points, int n, int stride, voi
     h->grid_n = 0;
     if (n == 0) return VG_OK;
     if (!d_points) return VG_ERR_ARG;
-    return cl_build_grid(h, d_points, n, stride, 3, (hipStream_t)stream);
+    // (the starting ClGrid is written on the device, as for vg_cluster_dbscan: a copy from this frame's stack, captured into a graph,
+    // would be read again at every replay)
+    return cl_build_grid(h, d_points, n, stride, 3, (hipStream_t)stream, true);
 }
 
 /* HOST ONLY (no GPU): the geometry the walks prune with, evaluated by the functions the kernels call (cl_origin, cl_cell_of,
