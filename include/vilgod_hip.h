@@ -777,6 +777,52 @@ size_t vg_boxes_nms_work_bytes(int n_rows, int max_group, int n_groups);
 int vg_boxes_nms_host(int box_dtype, const void* h_boxes, int score_dtype, const void* h_scores, const int32_t* h_off, int n_groups,
                       int n_rows, int max_group, int mode, double thresh, int pre_max, int32_t* h_keep, int32_t* h_count);
 
+/* Linear assignment: scipy.optimize.linear_sum_assignment, which the reference reaches in src/datasets/waymo_eval.py:111 (the
+ * matcher inside the detection metric) and calls in src/utils/tracking_utils.py:23-51.  Grouped: one call solves n_groups independent
+ * problems.  Group g has n_g = row_off[g+1] - row_off[g] rows and m_g = col_off[g+1] - col_off[g] columns, and its row-major float64
+ * cost matrix [n_g, m_g] starts at d_cost + cost_off[g]: the offset tables of vg_boxes_iou3d (a_off, b_off, out_off), so that kernel's
+ * output can be this one's input.  cost_len: the elements of d_cost.
+ *   problem     minimise the summed cost over injective partial assignments of rows to columns; a row may stay unassigned at the
+ *               price unassigned_cost (one double per call; NaN or -inf: VG_ERR_ARG).  +INFINITY: every row takes a column, the
+ *               classic problem, which needs n_g <= m_g.  An entry of +INFINITY forbids that pair.  Entries and prices whose sums
+ *               overflow float64 are outside the contract.
+ *   order       d_order (may be NULL: row order): int32, the entries row_off[g] .. row_off[g] + n_g - 1 are a permutation of
+ *               0 .. n_g - 1, the order in which group g's rows enter; n_rows: the entries of d_order (not read without it)
+ *   snapshots   after the k-th row has entered, the state is an optimal assignment of the first k rows.  d_prefix lists, per group,
+ *               strictly ascending prefix lengths in 1 .. n_g: group g's are d_prefix[prefix_off[g] .. prefix_off[g+1]) (prefix_off:
+ *               n_groups + 1 entries inside [0, n_snaps]).  Snapshot s (an index into d_prefix) is the group's col4row after
+ *               d_prefix[s] rows, n_g int32 at d_match + match_off[s]: the row's column, -1 for a row unassigned or not yet entered.
+ *               d_prefix == NULL (then prefix_off == NULL and n_snaps == n_groups): one snapshot per group after its last row, at
+ *               match_off[g].  match_len: the elements of d_match; what belongs to no snapshot is never written.
+ *   status      d_status int32 [n_groups]: 0 solved; 1 infeasible (a row with no finite choice left); 2 an entry is NaN or -INFINITY;
+ *               -1 the tables describe the group wrongly (n_g or m_g negative or above max_rows / max_cols, a matrix outside
+ *               [0, cost_len), order entries outside [0, n_rows), out of range or repeated, a prefix range outside [0, n_snaps], a
+ *               prefix length outside 1 .. n_g or not ascending, a snapshot outside [0, match_len)).  For any status but 0 every
+ *               snapshot of the group that lies inside d_match is filled with -1 (min(n_g, max_rows) entries).  Both forms check what
+ *               they read: nothing is read or written out of range.
+ *   algorithm   shortest augmenting paths with dual variables (the algorithm scipy uses), float64 throughout.  The next column is the
+ *               one of smallest path cost; among equal costs a free column wins, then the lowest column index, "stay unassigned"
+ *               counting as a free column behind all real ones (row i's is column m_g + i).  This tie rule is the project's own:
+ *               scipy's order among ties depends on its internal permutation and cannot be restated in parallel.  Where the optimum
+ *               is unique the assignments are scipy's; among ties the total is.
+ * vg_lap_groups: device pointers; ONE launch on `stream` (csrc/lap.hip: one wave per group), sized from n_groups, max_rows and max_cols
+ * alone: no read-back, no synchronisation, no allocation, no atomics -- it can be captured into a graph and gives the same bits on
+ * every run.  max_rows / max_cols: the caller's upper bounds on any group's size, at most VG_LAP_MAX each.
+ * vg_lap_groups_host: the same arguments over host arrays, the same per-column steps (csrc/lap_step.inc) run one after the other; the
+ * two agree bit for bit in every snapshot and status, ties included.  No GPU needed.
+ * VG_ERR_ARG (nothing launched): a negative count or length, max_rows / max_cols above VG_LAP_MAX, unassigned_cost NaN or -INFINITY,
+ * d_prefix without prefix_off or the reverse, d_prefix == NULL with n_snaps != n_groups, null pointers with non-empty work.
+ * n_groups == 0: VG_OK, nothing launched. */
+#define VG_LAP_MAX 1024
+int vg_lap_groups(const double* d_cost, int64_t cost_len, const int64_t* d_cost_off, const int32_t* d_row_off,
+                  const int32_t* d_col_off, int n_groups, int n_rows, int max_rows, int max_cols, double unassigned_cost,
+                  const int32_t* d_order, const int32_t* d_prefix, const int32_t* d_prefix_off, int n_snaps,
+                  const int64_t* d_match_off, int64_t match_len, int32_t* d_match, int32_t* d_status, void* stream);
+int vg_lap_groups_host(const double* h_cost, int64_t cost_len, const int64_t* h_cost_off, const int32_t* h_row_off,
+                       const int32_t* h_col_off, int n_groups, int n_rows, int max_rows, int max_cols, double unassigned_cost,
+                       const int32_t* h_order, const int32_t* h_prefix, const int32_t* h_prefix_off, int n_snaps,
+                       const int64_t* h_match_off, int64_t match_len, int32_t* h_match, int32_t* h_status);
+
 /* Points in boxes: pcdet's roiaware_pool3d_utils.points_in_boxes_gpu, which the reference calls in src/utils/pointcloud_utils.py:144-158
  * (get_box_heights) and :516-522 (points_in_boxes; src/vilgod/lidar_frame.py:154-161 turns box proposals into detections with it).
  * Per point the LOWEST index of a box that contains it, -1 when none does.  A box is a row of 7 values {cx, cy, cz, dx, dy, dz, rz},

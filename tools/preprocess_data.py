@@ -289,7 +289,8 @@ def main(argv=None):
         ap_dict = dataset.evaluation(detection_results, class_names=dataset.class_names, indices=indices, eval_cfg=cfg.eval_cfg,
                                      class_agnostic=det3d_cfg['class_agnostic'], eval_range=det3d_args['eval_range'], bev=det3d_cfg['bev'],
                                      moving=det3d_args['moving'], static=det3d_args['static'], score_thresh=det3d_cfg['score_thresh'],
-                                     sampling_rate=det3d_cfg['sampling_rate'], iou=str(cfg.get('device', {}).get('eval_iou', 'host')))
+                                     sampling_rate=det3d_cfg['sampling_rate'], iou=str(cfg.get('device', {}).get('eval_iou', 'host')),
+                                     match=str(cfg.get('device', {}).get('eval_match', 'host')))
         if isinstance(ap_dict, dict):
             from vilgod_amd.evaluation import print_eval_log
             print_eval_log(ap_dict, logger)

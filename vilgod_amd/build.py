@@ -36,6 +36,7 @@ SOURCES = {
     'lshape.hip': ['-ffp-contract=off'],
     'iou.hip': ['-ffp-contract=off'],
     'nms.hip': ['-ffp-contract=off'],
+    'lap.hip': ['-ffp-contract=off'],
     'clip_topk.hip': ['-ffp-contract=off'],
     'points_in_boxes.hip': ['-ffp-contract=off'],
     'oriented_extent.hip': ['-ffp-contract=off'],

@@ -115,14 +115,11 @@ def _check_iou_backend(iou):
     return iou
 
 
-def iou3d_matrices_device(pairs):
-    """[(a [na,>=7], b [nb,>=7]), ...] -> [float64 [na,nb], ...]: every matrix of the list in ONE launch of the rotated-box IoU kernel
-    (vilgod_amd/iou.py iou_groups, csrc/iou.hip).  Float32 boxes are widened exactly, as iou3d_matrix widens them."""
+def _iou3d_groups_device(pairs):
+    """[(a [na,>=7], b [nb,>=7]), ...] (not empty) -> (flat float64 CUDA tensor, out_off): every matrix of the list from
+    ONE launch of the rotated-box IoU kernel, left on the device; pair g's row-major [na, nb] matrix starts at out_off[g]."""
     import torch
     from .iou import iou_groups
-    pairs = [tuple(np.asarray(x).reshape(-1, np.shape(x)[-1] if np.ndim(x) == 2 else 7)[:, :7] for x in ab) for ab in pairs]
-    if not pairs:
-        return []
     dt = np.float32 if all(x.dtype == np.float32 for ab in pairs for x in ab) else np.float64
     a_off = np.cumsum([0] + [len(a) for a, _ in pairs])
     b_off = np.cumsum([0] + [len(b) for _, b in pairs])
@@ -130,8 +127,82 @@ def iou3d_matrices_device(pairs):
     b_all = np.concatenate([b for _, b in pairs]).astype(dt, copy=False)
     flat, out_off = iou_groups(torch.from_numpy(np.ascontiguousarray(a_all)).cuda(), a_off,
                                torch.from_numpy(np.ascontiguousarray(b_all)).cuda(), b_off)
+    return flat, out_off
+
+
+def _as_box_pairs(pairs):
+    return [tuple(np.asarray(x).reshape(-1, np.shape(x)[-1] if np.ndim(x) == 2 else 7)[:, :7] for x in ab) for ab in pairs]
+
+
+def iou3d_matrices_device(pairs):
+    """[(a [na,>=7], b [nb,>=7]), ...] -> [float64 [na,nb], ...]: every matrix of the list in ONE launch of the rotated-box IoU kernel
+    (vilgod_amd/iou.py iou_groups, csrc/iou.hip).  Float32 boxes are widened exactly, as iou3d_matrix widens them."""
+    pairs = _as_box_pairs(pairs)
+    if not pairs:
+        return []
+    flat, out_off = _iou3d_groups_device(pairs)
     flat = flat.cpu().numpy()
     return [flat[o:o + len(a) * len(b)].reshape(len(a), len(b)) for o, (a, b) in zip(out_off, pairs)]
+
+
+MATCH_BACKENDS = ('host', 'device', 'reference')
+
+
+def _check_match_backend(match):
+    if match not in MATCH_BACKENDS:
+        raise ValueError(f"match must be one of {MATCH_BACKENDS}, not {match!r}")
+    return match
+
+
+def match_order_and_prefixes(scores, cutoffs):
+    """What the metric's score cut-offs ask of the assignment solver for one (frame, type) group: the predictions in descending score
+    order (prediction index ascending among equal scores) and the distinct sizes > 0 of the kept sets `score >= cutoff`, ascending.
+    Every kept set is a prefix of that order."""
+    scores = np.asarray(scores, np.float64)
+    order = np.argsort(-scores, kind='stable').astype(np.int32)
+    kept = (scores[None, :] >= np.asarray(cutoffs, np.float64)[:, None]).sum(axis=1)
+    return order, np.unique(kept[kept > 0]).astype(np.int32)
+
+
+def _match_tables(groups, cutoffs, match, device_iou=None):
+    """The assignment of every (frame, type) group at every distinct kept set, from ONE call of the grouped solver (vilgod_amd/lap.py).
+    groups: [(w [np, ng] or None, scores [np])]; with device_iou = (flat CUDA IoU, out_off, thresholds per group) the weights are formed
+    on the device from the IoU kernel's output and `w` is not read.  match: 'device' = vg_lap_groups, 'reference' = vg_lap_groups_host
+    (the same steps on the CPU).  -> [{kept-set size: col4row int array [np]}]: the column of every prediction, -1 for none."""
+    from . import lap
+    shapes = [(len(sc), 0 if w is None else w.shape[1]) for w, sc in groups] if device_iou is None else device_iou[3]
+    row_off = np.cumsum([0] + [n for n, _ in shapes])
+    col_off = np.cumsum([0] + [m for _, m in shapes])
+    plans = [match_order_and_prefixes(sc, cutoffs) for _, sc in groups]
+    order = np.concatenate([o for o, _ in plans] + [np.zeros(0, np.int32)]).astype(np.int32)
+    prefixes = [p for _, p in plans]
+    if device_iou is not None:
+        import torch
+        flat, cost_off, thr, _ = device_iou
+        sizes = np.array([n * m for n, m in shapes], np.int64)
+        if len(flat) != int(sizes.sum()):
+            raise ValueError('the IoU matrices are not packed one behind the other')
+        thr_el = torch.repeat_interleave(torch.tensor(thr, dtype=torch.float64, device=flat.device),
+                                         torch.from_numpy(sizes).to(flat.device))
+        cost = -torch.where((flat >= thr_el) & (flat > 0), flat, torch.zeros_like(flat))
+    else:
+        sizes = np.array([n * m for n, m in shapes], np.int64)
+        cost_off = np.cumsum(sizes) - sizes
+        cost = -np.concatenate([w.reshape(-1) for w, _ in groups] + [np.zeros(0)])
+    if match == 'device':
+        import torch
+        if not torch.is_tensor(cost):
+            cost = torch.from_numpy(cost).cuda()
+        table, match_off, snap_off, status = lap.lap_groups(cost, cost_off, row_off, col_off, 0.0, order, prefixes)
+        table, status = table.cpu().numpy(), status.cpu().numpy()           # the match tables come down in one copy
+    else:
+        table, match_off, snap_off, status = lap.lap_groups_host(cost, cost_off, row_off, col_off, 0.0, order, prefixes)
+    if np.any(status != 0):
+        raise ValueError(f'the assignment solver refused group {int(np.flatnonzero(status != 0)[0])}: status {int(status[status != 0][0])}')
+    out = []
+    for g, (n, _) in enumerate(shapes):
+        out.append({int(k): table[match_off[s]:match_off[s] + n] for k, s in zip(prefixes[g], range(snap_off[g], snap_off[g + 1]))})
+    return out
 
 
 # ---- the adapters' `evaluation` up to the metric (pinned) -----------------------------------------------------------------------
@@ -317,10 +388,14 @@ def _average_precision(precision, recall):
     return float(np.sum((r - r_next) * p))
 
 
-def detection_metrics(pd_frame, pd_box, pd_type, pd_score, gt_frame, gt_box, gt_type, gt_difficulty, config, iou='host'):
+def detection_metrics(pd_frame, pd_box, pd_type, pd_score, gt_frame, gt_box, gt_type, gt_difficulty, config, iou='host', match='host'):
     """-> {'<BREAKDOWN>_<TYPE>[_<range>]_LEVEL_<L>/AP' | '/APH': [value]} (the key layout of the TF metric ops).
-    iou: 'host' = iou3d_matrix per (frame, type); 'device' = the IoU of every (frame, type) from one kernel launch (csrc/iou.hip)."""
+    iou: 'host' = iou3d_matrix per (frame, type); 'device' = the IoU of every (frame, type) from one kernel launch (csrc/iou.hip).
+    match: 'host' = scipy's linear_sum_assignment per (frame, type, distinct kept set); 'device' = every group at every kept set from
+    one launch of the grouped assignment kernel (csrc/lap.hip), the rows entering in score order; 'reference' = that solver's host form
+    (no GPU: the seam the CPU tests use).  With iou='device' as well the IoU matrices go from one kernel to the other on the device."""
     _check_iou_backend(iou)
+    _check_match_backend(match)
     cutoffs = np.asarray(config['score_cutoffs'], np.float64)
     nc = len(cutoffs)
     shards = []                                                     # (key prefix, type, r_lo, r_hi)
@@ -335,16 +410,33 @@ def detection_metrics(pd_frame, pd_box, pd_type, pd_score, gt_frame, gt_box, gt_
     pd_rng = np.linalg.norm(np.asarray(pd_box)[:, :3], axis=1) if len(pd_box) else np.zeros(0)
     gt_rng = np.linalg.norm(np.asarray(gt_box)[:, :3], axis=1) if len(gt_box) else np.zeros(0)
     frames = np.union1d(np.unique(pd_frame), np.unique(gt_frame))
-    from_device = None
-    if iou == 'device':                                             # the groups the loop below walks, in its order, in one launch
-        groups = []
+    from_device = tables = None
+    if iou == 'device' or match != 'host':                          # the groups the loop below walks, in its order
+        groups, members = [], []
         for f in frames:
             pi_f, gi_f = np.flatnonzero(pd_frame == f), np.flatnonzero(gt_frame == f)
             for t in (1, 2, 3, 4):
                 pi, gi = pi_f[pd_type[pi_f] == t], gi_f[gt_type[gi_f] == t]
                 if len(pi) or len(gi):
                     groups.append((np.asarray(pd_box, np.float64)[pi], np.asarray(gt_box, np.float64)[gi]))
-        from_device = iter(iou3d_matrices_device(groups))
+                    members.append((pi, t))
+        thr_of = [config['iou_thresholds'][t] for _, t in members]
+        if iou == 'device' and groups:                              # every IoU matrix in one launch ...
+            pairs = _as_box_pairs(groups)
+            flat, out_off = _iou3d_groups_device(pairs)
+            if match == 'device':                                   # ... and from there into the solver without a visit to the host
+                tables = iter(_match_tables([(None, pd_score[pi]) for pi, _ in members], cutoffs, match,
+                                            device_iou=(flat, out_off, thr_of, [(len(a), len(b)) for a, b in pairs])))
+            flat = flat.cpu().numpy()                               # (once, for the heading / w > 0 reads below)
+            mats = [flat[o:o + len(a) * len(b)].reshape(len(a), len(b)) for o, (a, b) in zip(out_off, pairs)]
+        elif iou == 'device':
+            mats = []
+        else:
+            mats = [iou3d_matrix(a, b) for a, b in groups]
+        from_device = iter(mats)
+        if match != 'host' and tables is None:
+            ws = [np.where((m >= thr) & (m > 0), m, 0.0) for m, thr in zip(mats, thr_of)]
+            tables = iter(_match_tables([(w, pd_score[pi]) for w, (pi, _) in zip(ws, members)], cutoffs, match))
     for f in frames:
         pi_f, gi_f = np.flatnonzero(pd_frame == f), np.flatnonzero(gt_frame == f)
         for t in (1, 2, 3, 4):
@@ -357,11 +449,18 @@ def detection_metrics(pd_frame, pd_box, pd_type, pd_score, gt_frame, gt_box, gt_
             sc = pd_score[pi]
             g_lvl = gt_difficulty[gi]
             prev_keep, match_p = None, None
+            table = None if tables is None else next(tables)
             for ci, cut in enumerate(cutoffs):
                 keep = np.flatnonzero(sc >= cut)
                 if prev_keep is None or len(keep) != len(prev_keep):        # same prediction set => same assignment
                     match_p = np.full(len(pi), -1)
-                    if len(keep) and len(gi):
+                    if table is not None:
+                        if len(keep) and len(gi):
+                            col = table[len(keep)]
+                            rr = np.flatnonzero(col >= 0)
+                            good = w[rr, col[rr]] > 0
+                            match_p[rr[good]] = col[rr[good]]
+                    elif len(keep) and len(gi):
                         rr, cc = linear_sum_assignment(-w[keep])
                         good = w[keep][rr, cc] > 0
                         match_p[keep[rr[good]]] = cc[good]
@@ -396,9 +495,10 @@ def detection_metrics(pd_frame, pd_box, pd_type, pd_score, gt_frame, gt_box, gt_
     return out
 
 
-def waymo_evaluation(prediction_infos, gt_infos, class_name, distance_thresh=100, fake_gt_infos=True, cfg=None, iou='host'):
-    """waymo_eval.py:197-231.  iou: detection_metrics' switch."""
+def waymo_evaluation(prediction_infos, gt_infos, class_name, distance_thresh=100, fake_gt_infos=True, cfg=None, iou='host', match='host'):
+    """waymo_eval.py:197-231.  iou, match: detection_metrics' switches."""
     _check_iou_backend(iou)
+    _check_match_backend(match)
     assert len(prediction_infos) == len(gt_infos), '%d vs %d' % (len(prediction_infos), len(gt_infos))
     pd_frame, pd_box, pd_type, pd_score, pd_nlz, _ = waymo_type_results(prediction_infos, class_name, is_gt=False)
     gt_frame, gt_box, gt_type, gt_score, _, gt_diff = waymo_type_results(gt_infos, class_name, is_gt=True, fake_gt_infos=fake_gt_infos)
@@ -406,7 +506,8 @@ def waymo_evaluation(prediction_infos, gt_infos, class_name, distance_thresh=100
     gt_box, gt_frame, gt_type, gt_score, gt_diff = mask_by_distance(distance_thresh, gt_box, gt_frame, gt_type, gt_score, gt_diff)
     if len(pd_score) and pd_score.max() > 1:
         pd_score = 1 / (1 + np.exp(-pd_score))
-    return detection_metrics(pd_frame, pd_box, pd_type, pd_score, gt_frame, gt_box, gt_type, gt_diff, build_config(**dict(cfg or {})), iou=iou)
+    return detection_metrics(pd_frame, pd_box, pd_type, pd_score, gt_frame, gt_box, gt_type, gt_diff, build_config(**dict(cfg or {})), iou=iou,
+                             match=match)
 
 
 def evaluate_detections(dataset, det_annos, class_names, **kwargs):
@@ -415,7 +516,7 @@ def evaluate_detections(dataset, det_annos, class_names, **kwargs):
         raise NotImplementedError
     return waymo_evaluation(dets, gts, class_name=class_names, distance_thresh=1000,
                             fake_gt_infos=_get(dataset.dataset_cfg, 'INFO_WITH_FAKELIDAR', False), cfg=kwargs.get('eval_cfg', {}),
-                            iou=kwargs.get('iou', 'host'))
+                            iou=kwargs.get('iou', 'host'), match=kwargs.get('match', 'host'))
 
 
 _NAMES = {'TYPE_VEHICLE': 'Vehicle', 'TYPE_PEDESTRIAN': 'Pedestrian', 'TYPE_CYCLIST': 'Cyclist'}
